@@ -18,7 +18,7 @@ output) over them, measured on its own.
 
 One step = one collection window per GPU, exactly as the agent's workers run it (the controller's
 per-window epilogue -- metrics, attributions, outputs -- is run over the same windows after the
-timed region and reported as host_epilogue_us_per_window):
+timed region, with --full, and reported as host_epilogue_us_per_window):
 
   producer process (stands in for the kernel: the probes' records, already framed as the BPF
   ring buffer holds them, plus the rocprofiler tool's GPU-signal records and the spans)
@@ -34,7 +34,13 @@ timed region and reported as host_epilogue_us_per_window):
 Synthetic data: seeded fault-replay traces (pipeline/replay.py, REF fault profiles plus the two
 REF domains REF's generator has no profile for); the kernel's record path is the native probe model (runtime/csrc/probesim.h).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up (data, rings, the model's training), warms up, times the K steps and prints
+the result line. ``--full`` adds everything else the benchmark measures, each in a pass of its
+own after the timed region: the controller's host epilogue over the timed windows, the paced
+CPU-overhead windows, the held-out attribution windows and REF's 55 rows (their fields of the
+result line are null / empty without it).
 """
 
 from __future__ import annotations
@@ -108,6 +114,13 @@ def parse():
                     help="user-space ring record size: 16 = USER16 (the rocprof tool's and samplers' compact slot; "
                          "a traced record takes two), 24 = USER24, 32 = USER32, 64 = EVENT")
     ap.add_argument("--out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: the controller's "
+                         "host epilogue over the timed windows, the paced CPU-overhead windows (--paced-windows), the "
+                         "held-out attribution windows (--heldout) and REF's 55 rows (none of them runs without it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step's window computed (its packet and "
+                         "incident results, as the worker hands them to the controller) as DIR/<name>.npy")
     ap.add_argument("--launch-probe", action="store_true",
                     help="rank bring-up only: join the process group, print the world JSON line, exit (no GPU)")
     return ap.parse_args()
@@ -244,6 +257,8 @@ def main() -> int:
         return self_launch(a.gpus)
     if a.launch_probe:
         return launch_probe(a)
+    if not a.full:  # a plain run: the timed steps and what they need, nothing else
+        a.paced_windows = a.heldout = 0
     if a.hw_queues > 0:  # before anything initialises the HIP runtime
         os.environ["GPU_MAX_HW_QUEUES"] = str(a.hw_queues)
     # PyTorch first: it brings its own HIP runtime, which the native engine module then shares
@@ -344,10 +359,14 @@ def main() -> int:
     rb, ring_bytes = shrinking(lambda s: rt.Ringbuf.create_shm(names["ring"], s), want, pow2(2 * win_bytes))
     if ring_bytes != want:
         log(f"note: BPF ring reduced to {ring_bytes >> 20} MiB (shared memory)")
+    # the user-space and span rings follow it: room for as many windows as the BPF ring can hold at
+    # once (the producer blocks on whichever ring fills first, so a long run would reserve and
+    # page-lock tens of GiB beyond that which no window ever uses)
+    n_fit = min(max(24, n_win), ring_bytes // min(len(i.framed) for i in imgs + himgs) + len(train_imgs) + 2)
     n_user = max(1, max(len(i.user) for i in imgs + himgs))
-    user, _ = shrinking(lambda c: rt.HostRing(c, a.user_rec, names["user"]), pow2(max(24, n_win) * n_user),
+    user, _ = shrinking(lambda c: rt.HostRing(c, a.user_rec, names["user"]), pow2(n_fit * n_user),
                         pow2(2 * n_user))
-    spans, _ = shrinking(lambda c: rt.HostRing(c, 64, names["spans"]), pow2(max(24, n_win) * a.spans),
+    spans, _ = shrinking(lambda c: rt.HostRing(c, 64, names["spans"]), pow2(n_fit * a.spans),
                          pow2(2 * a.spans))
     cuts = rt.HostRing(1 << 12, 64, names["cuts"])
     n_flat = a.warmup + a.steps
@@ -496,8 +515,9 @@ def main() -> int:
                       "incidents_trained": int(round(stats.count.sum())), "active_domains": trained.meta["active_domains"]}
         # the same statistics with the seeded random-init table as the prior (the north star's
         # random-init configuration), scored on REF's rows on the host below
-        alt = mtrain.TrainConfig(seed=a.seed, init="random" if tcfg.init == "expert" else "expert")
-        alt_model = with_pairs(NaiveBayes_learned(stats, alt, T), rho, T)
+        if a.full:
+            alt = mtrain.TrainConfig(seed=a.seed, init="random" if tcfg.init == "expert" else "expert")
+            alt_model = with_pairs(NaiveBayes_learned(stats, alt, T), rho, T)
         if a.export_model and rank == 0:
             mtrain.save_model(a.export_model, trained)
         log(f"trained on {len(train_imgs)} windows in {train_s:.2f}s: T = {T:.3f} (held-out NLL {nll:.3f})")
@@ -545,7 +565,7 @@ def main() -> int:
                       import_cap=import_cap, xchg_cap=xchg, model_image=b"", split=world > 1)
     core = WorkerCore.adopt(spec, pipe, src)
     ctl = Agent(AgentOptions(engine=a.engine, metrics_bind="", output="jsonl", output_path=os.devnull, config="",
-                             window_groups=g_node, min_confidence=0.5)) if rank == 0 else None
+                             window_groups=g_node, min_confidence=0.5)) if rank == 0 and a.full else None
     svc_names = [f"svc-{g + 1}" for g in range(g_node)]
     epi = [0.0, 0]  # host epilogue seconds, windows
 
@@ -571,7 +591,7 @@ def main() -> int:
     c0, cw0 = core.collect_s, core.collect_wait_s
     for j in range(a.warmup, a.warmup + a.steps):
         rep = core.window(next_cut(), a.services, labels=imgs[j % len(imgs)].labels)
-        if rank == 0:
+        if ctl is not None:  # kept for the epilogue pass below
             collected.extend(rep["prevs"])
         last = rep["k"]
         kernel_recs += rep["staged"]["n_kernel"]
@@ -583,9 +603,11 @@ def main() -> int:
         dist.barrier()
     sync()
     elapsed = time.perf_counter() - t0
-    for prev in collected + (fin["prevs"] if rank == 0 else []):
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, fin["prevs"][-1], last)
+    for prev in collected + (fin["prevs"] if ctl is not None else []):
         epilogue(prev)
-    attributions_emitted = ctl.attributions_emitted if ctl is not None else 0
+    attributions_emitted = ctl.attributions_emitted if ctl is not None else None
     if ctl is not None:
         ctl.close()
     busy_cpu_pct, _, _ = meter.stop()
@@ -666,7 +688,7 @@ def main() -> int:
     src.drain()
     ref55 = {}
     fx = os.path.join(ROOT, "tests", "fixtures", "ref_multi_fault_samples.jsonl")
-    if rank == 0 and os.path.exists(fx):
+    if rank == 0 and a.full and os.path.exists(fx):
         from llm_slo_ebpf_toolkit_amd.models.train import host_scorer, ref55_report
 
         if gpu:
@@ -688,6 +710,7 @@ def main() -> int:
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": round(ms_per_step, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -759,14 +782,14 @@ def main() -> int:
         "host_numa_bound_cpus": len(numa_cpus) if numa_cpus else None,
         # the controller's per-window epilogue on rank 0 (agent/daemon.py Agent._emit_window over the
         # node-wide results the timed steps collected), run and timed AFTER the timed region: it is
-        # not part of ms_per_step
-        "host_epilogue_us_per_window": round(1e6 * epi[0] / max(epi[1], 1), 1),
+        # not part of ms_per_step (--full only)
+        "host_epilogue_us_per_window": round(1e6 * epi[0] / max(epi[1], 1), 1) if a.full else None,
         # the worker's host loop per timed step: all of it, collecting finished windows (packet and
         # results reads), and of that the time blocked waiting for a window's chain to finish
         "host_loop_us_per_step": round(1e6 * loop_s / max(a.steps, 1), 1),
         "host_collect_us_per_step": round(1e6 * coll_s / max(a.steps, 1), 1),
         "host_collect_wait_us_per_step": round(1e6 * coll_wait_s / max(a.steps, 1), 1),
-        "attributions_emitted_timed": int(attributions_emitted),
+        "attributions_emitted_timed": None if attributions_emitted is None else int(attributions_emitted),
         "topology": (f"agent --gpus {world}: one window worker per GPU on split rings (its own kernel / user-space / "
                      f"span rings, producers routing by service), agent/worker.py WorkerCore.window per step, "
                      f"controller epilogue on rank 0 timed separately (host_epilogue_us_per_window, not in ms_per_step)")
@@ -785,6 +808,29 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(out_dir: str, prev: dict, k: int) -> None:
+    """What the timed path handed back for its last window (agent/worker.py WorkerCore: the window's
+    packet and every worker's incident results), one ``<name>.npy`` per array: float32 stays
+    float32, everything else becomes float64 (exact for the 32-bit integer fields)."""
+    import numpy as np
+
+    assert prev["k"] == k, (prev["k"], k)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"packet": prev["packet"]}
+    for r, res in enumerate(prev["results"]):
+        for key, v in res.items():
+            arrays[f"results{r}_{key}"] = v
+    total = 0
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        if not (np.issubdtype(v.dtype, np.number) or v.dtype == np.bool_):
+            continue
+        v = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+        total += v.nbytes
+        assert total <= 64 << 20, f"--dump-outputs: more than 64 MB ({name})"
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def rt_uid() -> bytes:

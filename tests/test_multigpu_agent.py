@@ -416,7 +416,7 @@ def test_bench_runs_the_agents_worker_path_on_two_ranks(tmp_path):
     epilogue (Agent._emit_window) over every timed window, measured on its own."""
     out = tmp_path / "bench.json"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--engine", "cpu", "--model", "bayes",
-                        "--events", "4096", "--spans", "256", "--services", "8", "--windows", "2", "--heldout", "3",
+                        "--full", "--events", "4096", "--spans", "256", "--services", "8", "--windows", "2", "--heldout", "3",
                         "--paced-windows", "0", "--steps", "3", "--warmup", "1", "--ring-mib", "16",
                         "--train-windows", "0", "--out", str(out)],
                        capture_output=True, text=True, timeout=580, cwd=str(tmp_path))
@@ -436,10 +436,11 @@ def test_bench_trains_the_learned_model_on_the_host_engine(tmp_path):
     windows' sufficient statistics as the device does (its packets' statistics block), so the
     model trained from random-init priors scores the timed windows (it scored none before)."""
     out = tmp_path / "bench.json"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "cpu", "--events", "16384",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--engine", "cpu", "--full", "--events", "16384",
                         "--spans", "1024", "--services", "16", "--windows", "2", "--heldout", "0",
                         "--paced-windows", "0", "--steps", "3", "--warmup", "1", "--ring-mib", "16",
-                        "--train-windows", "8", "--train-events", "16384", "--train-spans", "1024", "--out", str(out)],
+                        "--train-windows", "8", "--train-events", "16384", "--train-spans", "1024", "--out", str(out),
+                        "--dump-outputs", str(tmp_path / "dump")],
                        capture_output=True, text=True, timeout=580, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(out.read_text())
@@ -447,6 +448,13 @@ def test_bench_trains_the_learned_model_on_the_host_engine(tmp_path):
     assert d["macro_f1_timed_windows"] >= 0.9
     assert d["incidents_scored_timed_windows"] == 3 * 16
     assert 0 < d["attributions_emitted_timed"] <= d["incidents_scored_timed_windows"]
+    assert d["full"] is True and d["ms_per_step"] > 0
+    # --dump-outputs: the last timed window's packet and incident results, float32 / float64 only
+    dump = {f[:-4]: np.load(str(tmp_path / "dump" / f)) for f in os.listdir(str(tmp_path / "dump"))}
+    assert {"packet", "results0_post", "results0_pred", "results0_feat"} <= set(dump)
+    assert all(v.dtype in (np.float32, np.float64) for v in dump.values())
+    assert dump["results0_post"].shape[0] == 16 and dump["results0_pred"].shape == (16,)
+    assert np.isfinite(dump["results0_post"][:, :10]).all()
 
 
 def test_prev_joiner_emits_windows_once_every_worker_reported_them():

@@ -31,7 +31,7 @@ case "${1:-reentry}" in
   reentry)
     $S "400|gputests|python -u -m pytest tests -m gpu -x -v --timeout 150 --timeout-method thread" \
        "200|smoke|python3 -c 'import __graft_entry__ as g; g.smoke()'" \
-       "300|bench|python -u bench.py" \
+       "300|bench|python -u bench.py --full" \
        "300|trace|rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d gpurun_out/trace -- python3 bench.py --steps 20 --warmup 3 --paced-windows 0" ;;
   pmc)
     $S "150|pmc1|$P SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES -d gpurun_out/pmc1 -- $B" \
@@ -58,7 +58,7 @@ case "${1:-reentry}" in
   branch)   # GPU tests, then the bench with and without the span branch stream, and a kernel trace
     $S "400|gputests|python -u -m pytest tests -m gpu -x -v --timeout 150 --timeout-method thread" \
        "200|smoke|python3 -c 'import __graft_entry__ as g; g.smoke()'" \
-       "300|bench|python -u bench.py" \
+       "300|bench|python -u bench.py --full" \
        "300|bench_nobranch|MISLO_SPAN_STREAM=0 python -u bench.py" \
        "300|bench_branch_hiprio|MISLO_SPAN_STREAM_PRIO=1 python -u bench.py" \
        "300|trace|rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d gpurun_out/trace -- python3 bench.py --steps 20 --warmup 3 --paced-windows 0" ;;
@@ -86,7 +86,7 @@ case "${1:-reentry}" in
   final)    # round 5's final validation: every GPU test, smoke, the bench at K = 20 and 100, a kernel + copy trace
     $S "500|gputests|python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread" \
        "200|smoke|python3 -c 'import __graft_entry__ as g; g.smoke()'" \
-       "300|bench|python -u bench.py" \
+       "300|bench|python -u bench.py --full" \
        "300|bench100|python -u bench.py --steps 100 --warmup 10" \
        "300|trace|rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d gpurun_out/trace_final -- python3 bench.py --steps 20 --warmup 3 --paced-windows 0" ;;
   overhead5) # the shipped agent at 1M events/s, shipped configuration (3 runs) and built-in defaults
@@ -95,7 +95,7 @@ case "${1:-reentry}" in
        "200|oh_3|$O --out gpurun_out/r5_oh_3.json" "200|oh_bare|$O --bare --out gpurun_out/r5_oh_bare.json" ;;
   probe)    # the join's oracle tests (headline shape included), the bench, a kernel trace ($2: out tag)
     $S "420|native|python -u -m pytest tests/test_native_engine.py tests/test_gpu_engine.py -m gpu -x -v --timeout 360 --timeout-method thread" \
-       "300|bench|python -u bench.py" \
+       "300|bench|python -u bench.py --full" \
        "300|trace|rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/trace_${2:-probe} -- python3 bench.py --steps 20 --warmup 3 --paced-windows 0" ;;
   rss)
     $S "120|rss_q1|GPU_MAX_HW_QUEUES=1 python tools/rss_probe.py" \
