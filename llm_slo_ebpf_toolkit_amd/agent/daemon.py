@@ -208,6 +208,10 @@ class AgentOptions:
     # (profiles/r6_uprobe/); the KFD sampler's activity decision does without them
     hip_launch_uprobes: bool = False
     pair_prior: float = 0.0              # 2-fault prior mass added to a table model without pairs (0 = none)
+    # count a TTFT breach when a request's deadline passes with no first token (start records,
+    # pipeline/openreq.py), not when the late first token arrives; one GPU; nothing is checkpointed
+    deadline_breach: bool = False
+    open_requests_cap: int = 1 << 20     # entries of the open-request table
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -722,6 +726,8 @@ class Agent:
                     "burn_now": round(cur, 4), "burn_forecast": round(burn, 4),
                     "top": [[p.domain, round(float(p.posterior), 4)] for p in ranked[:3]],
                     "late": late_l[g] if g < len(late_l) else 0, "emitted": emit,
+                    **({"deadline": res["deadline"][g].tolist()} if res.get("deadline") is not None
+                       and g < len(res["deadline"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -786,6 +792,8 @@ class Agent:
         self.metrics.set_ring(ring.stats() if ring is not None else {}, rs, max(p["host_us"] for p in prevs))
         res = merge_results(head["results"], G)
         self.last_results = res
+        if head.get("open_requests") is not None and res.get("deadline") is not None:
+            self.metrics.observe_open_requests(res["deadline"], head["open_requests"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -891,6 +899,9 @@ class Agent:
         o = self.o
         N = self.n_gpus()
         split = N > 1 and o.split_rings
+        if o.deadline_breach and N > 1:
+            raise ValueError("--deadline-breach runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the open-request corrections are applied on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -933,7 +944,9 @@ class Agent:
                             window_ms=float(o.window_ms), ttft_slo_ms=o.ttft_slo_ms, halo_ms=o.halo_ms,
                             import_cap=icap, xchg_cap=xchg, model_image=np.asarray(image, np.uint8).tobytes(),
                             pods=pods, master=("127.0.0.1", port), halo_windows=halo_windows, split=split,
-                            app_image=app_model_bytes(model).tobytes() if model.app is not None else b"")
+                            app_image=app_model_bytes(model).tobytes() if model.app is not None else b"",
+                            open_requests=int(o.open_requests_cap) if o.deadline_breach else 0,
+                            open_reorder_ms=2.0 * float(o.window_ms))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

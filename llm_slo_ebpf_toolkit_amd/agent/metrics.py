@@ -86,6 +86,18 @@ class AgentMetrics:
                               "pod memory limit is enforced on, next to RSS.")
         self.burn_err = r.gauge("llm_slo_agent_burn_rate_prediction_error",
                                 "Mean relative error of the scored SLO burn-rate forecasts.")
+        # the open-request tracker (agent --deadline-breach, pipeline/openreq.py)
+        self.deadline_breaches = r.counter("llm_slo_agent_deadline_breaches_total",
+                                           "TTFT breaches counted when the request's deadline passed with no first "
+                                           "token (start records, --deadline-breach), by service.", ("service",))
+        self.open_requests = r.gauge("llm_slo_agent_open_requests",
+                                     "Rows of the open-request table by state: open (started, no first token), "
+                                     "counted (breach counted at its deadline, not reported yet), resolved (an "
+                                     "SLI that came ahead of its start record).", ("state",))
+        self.open_events = r.counter("llm_slo_agent_open_request_events_total",
+                                     "Open-request table events: dup_start, start_after_sli, dropped_full, expired "
+                                     "(counted, never reported within the ttl), false_deadline (counted, then "
+                                     "reported within the SLO).", ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -192,6 +204,18 @@ class AgentMetrics:
                            ("spoofed", getattr(mapper, "spoofed", 0)),
                            ("first_token_late", getattr(mapper, "early_dropped", 0))):
             self.otlp.set(float(v), outcome)
+
+    def observe_open_requests(self, deadline: np.ndarray, stats: dict, names) -> None:
+        """One window of the open-request tracker: ``deadline`` [G, 2] (this window's, earlier
+        windows'), ``stats`` by name (pipeline/openreq.py STATS)."""
+        d = np.asarray(deadline, dtype=np.int64).sum(axis=1).tolist()
+        for g, n in enumerate(d):
+            if n:
+                self.deadline_breaches.inc(float(n), names[g] if g < len(names) else f"group-{g}")
+        for state in ("open", "counted", "resolved"):
+            self.open_requests.set(float(stats.get("live_" + state, 0)), state)
+        for reason in ("dup_start", "start_after_sli", "dropped_full", "expired", "false_deadline"):
+            self.open_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

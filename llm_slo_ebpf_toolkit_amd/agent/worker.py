@@ -79,6 +79,8 @@ class WorkerSpec:
     halo_windows: int = 3       # earlier windows resident on the device for the halo
     split: bool = False         # split rings: this worker's own ring set (RingNames.of(ring_name, rank))
     app_image: bytes = b""      # the application evidence model (ops/engine.py app_model_bytes); empty: off
+    open_requests: int = 0      # entries of the open-request table (agent --deadline-breach); 0: off
+    open_reorder_ms: float = 2000.0
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -91,7 +93,8 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     (group g = local g // world of worker g % world)."""
     world = len(parts)
     out = {}
-    for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late"):
+    for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
+                "deadline_dup"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -159,7 +162,8 @@ class WorkerCore:
                                    import_cap=spec.import_cap,
                                    xchg_cap=spec.xchg_cap, shard=(spec.rank, spec.world), engine=spec.engine,
                                    group=group, model_image=np.frombuffer(spec.model_image, dtype=np.uint8),
-                                   split_rings=spec.split)
+                                   split_rings=spec.split, open_requests=spec.open_requests,
+                                   open_reorder_ms=spec.open_reorder_ms)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -275,6 +279,10 @@ class WorkerCore:
         if self.spec.rank == 0:  # the node-wide packet and every worker's incidents (all-gathered)
             d["packet"] = pk
             d["results"] = pipe.results_all(k, n_groups) if self.spec.world > 1 else [pipe.results(k, n_groups)]
+            if pipe.tracker is not None:  # the open-request table's statistics of the window
+                from ..pipeline.openreq import stats_dict
+
+                d["open_requests"] = stats_dict(pipe.open_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:
@@ -287,7 +295,7 @@ class WorkerCore:
         return out
 
     def close(self) -> None:
-        self.pipe.eng.close()
+        self.pipe.close()
 
 
 # ---------------------------------------------------------------------------------------

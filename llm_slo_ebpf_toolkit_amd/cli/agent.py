@@ -107,6 +107,12 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         ("ttft-slo-ms", d.ttft_slo_ms, "per-incident TTFT SLO (ms) for burn rates"),
         ("slo-target", d.slo_target, "TTFT SLO objective for burn rates (0.99 = 1%% error budget)"),
         ("otlp-receiver-bind", d.otlp_receiver_bind, "OTLP/HTTP /v1/traces receiver feeding the span ring (gpu engine)"),
+        ("deadline-breach", False, "gpu engine: count a TTFT breach when a request's deadline (start + "
+                                   "--ttft-slo-ms) passes with no first token, from the services' start records "
+                                   "(llm.slo.request_start), instead of when the late first token arrives; one GPU "
+                                   "only; the table is not checkpointed"),
+        ("open-requests-cap", d.open_requests_cap, "--deadline-breach: entries of the open-request table (a power "
+                                                   "of two)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -154,7 +160,8 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         pair_prior=float(a.pair_prior), emit_wait_ms=int(a.emit_wait_ms), webhook_queue=int(a.webhook_queue),
         emit_min_burn=float(a.emit_min_burn), emit_min_requests=float(a.emit_min_requests),
         emit_recovered_requests=int(a.emit_recovered_requests),
-        decision_log=a.decision_log,
+        decision_log=a.decision_log, deadline_breach=bool(a.deadline_breach),
+        open_requests_cap=int(a.open_requests_cap),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -345,7 +345,8 @@ class SpanMapper:
     @staticmethod
     def is_request_span(d: dict) -> bool:
         attrs = d.get("attrs", {})
-        return not d.get("parentSpanId") or any(k in attrs for k in TTFT_KEYS)
+        return (not d.get("parentSpanId") or any(k in attrs for k in TTFT_KEYS)
+                or _truthy(attrs.get(semconv.ATTR_SLO_REQUEST_START)))
 
     def records(self, spans: List[Tuple[Dict[str, object], dict]], peer: str = "") -> np.ndarray:
         """Request spans -> SPAN records. A pod's service is bound by the first span that names
@@ -419,7 +420,12 @@ class SpanMapper:
             v = _first(a, TTFT_KEYS)
             th = trace_hash(d.get("traceId"))
             fl = 0
-            if th and v is not None:
+            # a start record (llm.slo.request_start, no TTFT yet): joins, never counts, and leaves
+            # the first-token / request-span pairing and the trace's retrieval breakdown alone
+            start = v is None and _truthy(a.get(semconv.ATTR_SLO_REQUEST_START))
+            if start:
+                fl = records.SPAN_START | records.SPAN_NO_SLI
+            elif th and v is not None:
                 if _truthy(a.get(semconv.ATTR_SLO_TTFT_EARLY)):
                     with self._rlock:
                         if self._final.pop(th, None) is not None:
@@ -440,8 +446,8 @@ class SpanMapper:
             flags.append(fl)
             # the trace's retrieval breakdown goes to its first record (a first-token record when the
             # service exports one), once: later records of the trace carry only what arrives with them
-            rv = retr.pop(th, None) if th else None
-            if self._retr and th:
+            rv = retr.pop(th, None) if th and not start else None
+            if self._retr and th and not start:
                 with self._rlock:
                     early = self._retr.pop(th, None)
                 if early is not None:
@@ -478,7 +484,8 @@ class SpanMapper:
             fl = np.asarray(flags, dtype=np.uint32)
             if late_before > 0 and slo_ns > 0:
                 t0s = np.asarray(ts, dtype=np.int64)
-                fl |= np.where((t0s > 0) & (t0s + slo_ns < late_before), records.SPAN_LATE, 0).astype(np.uint32)
+                fl |= np.where((t0s > 0) & (t0s + slo_ns < late_before) & ((fl & records.SPAN_START) == 0),
+                               records.SPAN_LATE, 0).astype(np.uint32)
             out["flags"] = fl
         return out
 

@@ -233,10 +233,13 @@ SPAN = np.dtype([
     # request span joins but does not count again; bit 2 (SPAN_FIRST_TOKEN): a first-token record
     # (exported when the first token is out, llm.slo.ttft_early) -- counted, and joined like the
     # request span (its keys but the connection: the request span brings the pod+conn tier), so the
-    # request's kernel evidence reaches the window its SLI is counted in
+    # request's kernel evidence reaches the window its SLI is counted in; bit 3 (SPAN_START): a start
+    # record (llm.slo.request_start: "this request started at ts_ns", ttft_ms NaN, always with
+    # SPAN_NO_SLI) -- joins, never counts; the open-request tracker (pipeline/openreq.py) reads it
     ("flags", "<u4"),
 ])
 SPAN_LATE, SPAN_NO_SLI, SPAN_FIRST_TOKEN = 1, 2, 4
+SPAN_START = 8
 assert SPAN.itemsize == 64
 
 FLAG_HAS_GPU = 1 << 8

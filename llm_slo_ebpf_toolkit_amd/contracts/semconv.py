@@ -17,6 +17,9 @@ ATTR_CORRELATION_CONF = "llm.ebpf.correlation_confidence"
 ATTR_SLO_TTFT_MS = "llm.slo.ttft_ms"
 # true on a record exported when the first token is out (the SLI, ahead of the request span)
 ATTR_SLO_TTFT_EARLY = "llm.slo.ttft_early"
+# true on a zero-duration span exported when a request starts (no TTFT yet): the agent's
+# open-request tracker counts a TTFT breach when start + SLO passes with no first token
+ATTR_SLO_REQUEST_START ="llm.slo.request_start"
 ATTR_SLO_TOKENS_PER_SEC = "llm.slo.tokens_per_sec"
 ATTR_RETRIEVAL_VECTORDB = "llm.slo.retrieval.vectordb_ms"
 ATTR_RETRIEVAL_NETWORK_MS = "llm.slo.retrieval.network_ms"

@@ -312,8 +312,12 @@ class VectorDBClient:
 class RagService:
     def __init__(self, backend, corpus_path: str = os.path.join(HERE, "fixtures", "corpus.json"),
                  otlp_endpoint: str = "", node: str = "demo-node", pod: str = "demo-rag-service", resource=None,
-                 vectordb_url: str = "", early_ttft: bool = True):
+                 vectordb_url: str = "", early_ttft: bool = True, export_start: bool = False):
         self.backend = backend
+        # say "request started" once, at the start (a zero-duration chat.start span,
+        # llm.slo.request_start): the agent's open-request tracker counts a TTFT breach when the
+        # deadline passes, not when the late first token arrives (agent --deadline-breach)
+        self.export_start = export_start
         # export the TTFT SLI when the first token is out (a chat.first_token span,
         # llm.slo.ttft_early), not only on the request span at the end: an SLO breach reaches the
         # agent's window it happened in (collector/otlp.py counts each request once)
@@ -356,6 +360,10 @@ class RagService:
         trace_id = hashlib.blake2b(rid.encode(), digest_size=16).hexdigest()
         root, rsp, gsp = (hashlib.blake2b(f"{rid}/{k}".encode(), digest_size=8).hexdigest() for k in "rxg")
         t_req = time.time_ns()
+        if self.export_start:
+            self.spans.add([SpanExporter.span(
+                trace_id, hashlib.blake2b(f"{rid}/s".encode(), digest_size=8).hexdigest(), root, "chat.start",
+                t_req, t_req, {semconv.ATTR_SLO_REQUEST_START: True})], urgent=True)
         plan = plan_for(profile, prompt, seed)
         rnd = random.Random(seed + prompt_hash(prompt))
         docs = sorted(d["title"] for d in rnd.sample(self.docs, min(plan.docs, len(self.docs))))
@@ -528,11 +536,15 @@ def main(argv=None) -> int:
     ap.add_argument("--otlp-endpoint", default=os.environ.get("OTEL_EXPORTER_OTLP_TRACES_ENDPOINT", ""))
     ap.add_argument("--early-ttft", type=int, default=1, help="1: export each request's TTFT when its first token "
                                                                 "is out (chat.first_token), not only at its end")
+    ap.add_argument("--export-start", type=int, default=0, help="1: export a chat.start span when a request starts "
+                                                                  "(the agent's --deadline-breach counts a TTFT "
+                                                                  "breach at its deadline)")
     ap.add_argument("--vectordb-url", default=os.environ.get("VECTORDB_URL", ""),
                     help="vector-DB stub (demo/vectordb.py) to search over a keep-alive connection")
     a = ap.parse_args(argv)
     backend = LlamaBackend(a.llama_preset) if a.backend == "llama" else StubBackend()
-    svc = RagService(backend, otlp_endpoint=a.otlp_endpoint, vectordb_url=a.vectordb_url, early_ttft=bool(a.early_ttft))
+    svc = RagService(backend, otlp_endpoint=a.otlp_endpoint, vectordb_url=a.vectordb_url, early_ttft=bool(a.early_ttft),
+                     export_start=bool(a.export_start))
     httpd, _ = svc.serve(a.bind, a.metrics_bind)
     print(f"rag-service listening on {a.bind} (backend={backend.name})", flush=True)
     try:

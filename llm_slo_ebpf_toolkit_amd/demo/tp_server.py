@@ -35,6 +35,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-new", type=int, default=16)
     ap.add_argument("--early-ttft", type=int, default=1, help="1: export each request's TTFT when its first token "
                                                                 "is out (chat.first_token), not only at its end")
+    ap.add_argument("--export-start", type=int, default=0, help="1: export a chat.start span when a request starts "
+                                                                  "(the agent's --deadline-breach counts a TTFT "
+                                                                  "breach at its deadline)")
     ap.add_argument("--device", default="cuda", choices=("cuda", "cpu"), help="cpu: the gloo rehearsal (tests)")
     a = ap.parse_args(argv)
 
@@ -110,6 +113,10 @@ def main(argv=None) -> int:
             # lock an attribute: the agent joins signals near the span's start, and a start
             # several queued requests back would fall outside the records it still holds
             t0 = time.time_ns()
+            if a.export_start:  # "request started", once: the agent's deadline clock starts here
+                spans.add([SpanExporter.span(
+                    trace, hashlib.blake2b(f"{rid}/s".encode(), digest_size=8).hexdigest(), root, "chat.start",
+                    t0, t0, {semconv.ATTR_SLO_REQUEST_START: True})], urgent=True)
             ids = torch.tensor([toks], dtype=torch.int64, device=dev)
             if world > 1:
                 th = trace_hash(trace)

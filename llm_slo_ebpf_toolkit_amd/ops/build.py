@@ -115,7 +115,7 @@ def build_hip_ext(force: bool = False, jobs: int = 4) -> str:
     return out
 
 
-AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip"]
+AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip", "openreq.hip"]
 
 
 def build_agent_ext(force: bool = False, jobs: int = 4) -> str:
@@ -128,7 +128,12 @@ def build_agent_ext(force: bool = False, jobs: int = 4) -> str:
     common += os.environ.get("MISLO_HIP_DEFINES", "").split()
     jobs_list, objs = [], []
     for src in AGENT_KERNELS:  # shared with the torch extension (same flags, same objects)
-        objs.append(os.path.join(BUILD, src + ".o"))
+        obj = os.path.join(BUILD, src + ".o")
+        objs.append(obj)
+        path = os.path.join(CSRC, src)
+        # kernels of the agent alone (the open-request tracker) are compiled here
+        if src not in HIP_SOURCES and (force or _newer(obj, [path] + hdrs)):
+            jobs_list.append([HIPCC, *common, "-c", path, "-o", obj])
     eng = os.path.join(CSRC, "engine.hip")
     eobj = os.path.join(BUILD, "engine.hip.o")
     objs.append(eobj)

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "engine.h"
+#include "openreq.h"
 
 namespace py = pybind11;
 using namespace mislo;
@@ -310,6 +311,85 @@ class PyEngine {
   std::unique_ptr<WindowEngine> e_;
 };
 
+// The open-request tracker (openreq.h): one step per window over the same span ranges the engine
+// gets; results per step index.
+class PyOpenRequests {
+ public:
+  PyOpenRequests(int device, int64_t cap, int span_cap, int group_cap, int n_buffers, double slo_ms, double ttl_ms,
+                 double reorder_ms) {
+    openreq::Config c;
+    c.device = device;
+    c.cap = cap;
+    c.span_cap = span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.slo_ms = slo_ms;
+    c.ttl_ms = ttl_ms;
+    c.reorder_ms = reorder_ms;
+    openreq::validate(c);
+    t_ = std::make_unique<OpenRequests>(c);
+  }
+  OpenRequests& t() {
+    if (!t_) throw std::logic_error("open-request tracker closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int64_t prev_cut_ns,
+               int n_groups) {
+    OpenRequests& tr = t();
+    py::gil_scoped_release nogil;
+    return tr.step(spans, cut_ns, prev_cut_ns, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    OpenRequests& tr = t();
+    if (n_groups < 0 || n_groups > tr.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = tr.results(i);
+    }
+    const openreq::Layout& l = tr.result_layout();
+    py::dict d;
+    d["dl"] = copy_array(r + l.dl, {n_groups, 2});
+    d["dup"] = copy_array(r + l.dup, {n_groups, 3});
+    d["stats"] = copy_array(r + l.stats, {openreq::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::pair<float, float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms.first, ms.second);
+  }
+  py::tuple entries() {
+    std::vector<uint64_t> k;
+    std::vector<int64_t> tt;
+    std::vector<uint32_t> g, s;
+    {
+      py::gil_scoped_release nogil;
+      t().entries(k, tt, g, s);
+    }
+    const py::ssize_t n = (py::ssize_t)k.size();
+    return py::make_tuple(copy_array(k.data(), {n}), copy_array(tt.data(), {n}), copy_array(g.data(), {n}),
+                          copy_array(s.data(), {n}));
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<OpenRequests> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -338,6 +418,22 @@ PYBIND11_MODULE(_mislo_agent, m) {
   m.attr("SIGREC_BYTES") = (int)sizeof(SigRec);
   m.attr("RING_STATE") =
       py::make_tuple("first_busy", "foreign", "def_ctx", "def_trace", "discarded", "events", "other_shard");
+  m.attr("OPENREQ_LDS_GROUPS") = openreq::kLdsGroups;
+  m.attr("OPENREQ_MAX_PROBES") = openreq::kMaxProbes;
+  m.attr("OPENREQ_STATS") = (int)openreq::kStats;
+  py::class_<PyOpenRequests>(m, "OpenRequests")
+      .def(py::init<int, int64_t, int, int, int, double, double, double>(), py::arg("device") = 0,
+           py::arg("cap") = (int64_t)1 << 20, py::arg("span_cap") = 16384, py::arg("group_cap") = 64,
+           py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("ttl_ms") = 120000.0,
+           py::arg("reorder_ms") = 2000.0)
+      .def("step", &PyOpenRequests::step, py::arg("spans"), py::arg("cut_ns"), py::arg("prev_cut_ns"),
+           py::arg("n_groups"))
+      .def("query", &PyOpenRequests::query)
+      .def("results", &PyOpenRequests::results)
+      .def("step_ms", &PyOpenRequests::step_ms)
+      .def("entries", &PyOpenRequests::entries)
+      .def("sync", &PyOpenRequests::sync)
+      .def("close", &PyOpenRequests::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

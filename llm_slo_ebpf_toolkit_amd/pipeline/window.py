@@ -95,7 +95,8 @@ class WindowPipeline:
                  max_ahead: int = 3, n_buffers: int = 3, user_cap: int = USER_CAP, ttft_slo_ms: float = 800.0,
                  halo_ms: float = 0.0, import_cap: int = 0, xchg_cap: int = 0, shard: Tuple[int, int] = (0, 1),
                  engine: str = "gpu", group=None, model_image: Optional[np.ndarray] = None, halo_windows: int = 3,
-                 split_rings: bool = False):
+                 split_rings: bool = False, open_requests: int = 0, open_ttl_ms: float = 120000.0,
+                 open_reorder_ms: Optional[float] = None):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -103,7 +104,13 @@ class WindowPipeline:
         ``split_rings``: the records arrive already routed to this worker's own rings (no record
         ownership filter; spans keep theirs).
         ``model_image``: a PosteriorModel image to score with (models/export.py) instead of ``model``'s
-        built-in initial model."""
+        built-in initial model.
+        ``open_requests`` > 0: track open requests in a table of that many entries and count TTFT
+        breaches when the deadline passes (pipeline/openreq.py; the device table for "gpu", the
+        host oracle for "cpu"); ``results()`` then returns corrected ``sli`` / ``late``. 0: off.
+        ``open_ttl_ms``: a counted request that never reports leaves the table after this long;
+        ``open_reorder_ms`` (default 2 x ``window_ms``): how long an SLI record that came ahead of
+        its start record is remembered. One GPU only (no communicator, no sharding)."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -157,6 +164,24 @@ class WindowPipeline:
             self.eng.set_model_bytes(model_bytes(self.model))
         self.k = 0
         self.windows_folded_host = 0
+        self.tracker = None
+        self.open_skipped = 0  # cuts without a time (replay helpers): no tracker step
+        self._open: Dict[int, Tuple[int, Optional[int]]] = {}  # buffer -> (window, tracker step)
+        if open_requests:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("open-request tracking runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            tkw = dict(cap=int(open_requests), span_cap=span_cap, group_cap=group_cap, n_buffers=self.nb,
+                       slo_ms=ttft_slo_ms, ttl_ms=open_ttl_ms,
+                       reorder_ms=2.0 * window_ms if open_reorder_ms is None else open_reorder_ms, device=device)
+            if engine == "gpu":
+                from ..ops.openreq import OpenRequestTable
+
+                self.tracker = OpenRequestTable(**tkw)
+            else:
+                from .openreq import OpenRequestOracle
+
+                self.tracker = OpenRequestOracle(**tkw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -230,7 +255,40 @@ class WindowPipeline:
 
     def results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
         self.eng.wait(k)
-        return self.eng.results(k, n_groups)
+        res = self.eng.results(k, n_groups)
+        if self.tracker is None:
+            return res
+        from .openreq import correct_results
+
+        return correct_results(res, self.open_results(k, n_groups))
+
+    # ---- open requests (pipeline/openreq.py) ------------------------------------------------
+    def track_open(self, spans, cut_ns: int, prev_cut_ns: int, n_groups: int) -> None:
+        """The tracker's step for the window about to be submitted: the same span ranges, the
+        cut's time and the previous cut's. A cut without a time is skipped and counted."""
+        if self.tracker is None:
+            return
+        step = None
+        if int(cut_ns) > 0:
+            step = self.tracker.step(list(spans), int(cut_ns), min(int(prev_cut_ns), int(cut_ns)), int(n_groups))
+        else:
+            self.open_skipped += 1
+        self._open[self.k % self.nb] = (self.k, step)
+
+    def open_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The tracker's dl / dup / stats of window k (zeros for a window it skipped)."""
+        held = self._open.get(k % self.nb)
+        if held is not None and held[0] == k and held[1] is not None:
+            return self.tracker.results(held[1], n_groups)
+        from .openreq import N_STATS
+
+        return {"dl": np.zeros((n_groups, 2), np.uint32), "dup": np.zeros((n_groups, 3), np.uint32),
+                "stats": np.zeros(N_STATS, np.uint32)}
+
+    def close(self) -> None:
+        if self.tracker is not None:
+            self.tracker.close()
+        self.eng.close()
 
     def results_all(self, k: int, n_groups: int) -> List[Dict[str, np.ndarray]]:
         """Every GPU's incident results of window k (RCCL all-gather; this GPU's alone when the
@@ -266,6 +324,8 @@ class WindowPipeline:
     # ---- totals / model ---------------------------------------------------------------------
     def drain(self) -> None:
         self.eng.sync()
+        if self.tracker is not None:
+            self.tracker.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -419,6 +479,7 @@ class RingWindowSource:
         self.resubmitted = 0
         self.carried = 0   # records past a window's budget, summed over windows (should stay 0)
         self.reap_s = self.submit_s = 0.0  # host time: waiting for / reading back finished windows, submitting
+        self.prev_cut_ns = 0  # the last timed cut (the open-request tracker's previous cut)
 
     def publish_epoch(self, now_ns: Optional[int] = None) -> int:
         v = self.clock.publish(int(now_ns if now_ns is not None else time.time_ns()))
@@ -561,6 +622,10 @@ class RingWindowSource:
             self.carried += max(0, cut.spans - self.spos) - n_s
             self.spos += n_s
         wl = labels is not None if with_labels is None else with_labels
+        if pipe.tracker is not None:  # the open requests see the window's spans and the cut's time
+            pipe.track_open(spans, cut.t_ns, self.prev_cut_ns, n_groups)
+            if int(cut.t_ns) > 0:
+                self.prev_cut_ns = int(cut.t_ns)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
