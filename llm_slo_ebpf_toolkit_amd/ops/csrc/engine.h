@@ -22,6 +22,10 @@
 // where their own window decoded and partitioned them -- and the other GPUs' trace-tagged rows of
 // window k (exchange.hip), so joins across window and GPU boundaries match.
 //
+// One GPU without the exchange: the graph is split at the probe into a front stage on a front
+// stream and a back stage on the compute stream, and window k+1's front runs beside window k's
+// back (window overlap, below at front_).
+//
 // so the DMA of window k+1 and the node-wide all-reduce of window k run under the kernels of
 // window k+1. The whole compute chain of a buffer is captured once into a HIP graph and
 // replayed (one launch per window). Host waits use blocking-sync events (no spin: the
@@ -198,10 +202,15 @@ class WindowEngine {
   int rec_shard_rank() const { return cfg_.split_rings ? 0 : cfg_.shard_rank; }
   int rec_shard_world() const { return cfg_.split_rings ? 1 : cfg_.shard_world; }
   void alloc();
+  void enable_span_branch();  // side_, its events, branch_ (alloc; init_comm leaving the overlap)
   void set_buffer(int b);
   void run_begin(int b, hipStream_t st);
   void run_part1(int b, hipStream_t st, bool xchg);
   void run_part2(int b, int n_groups, bool with_labels, bool learn, hipStream_t st, bool xchg);
+  // run_part2's two halves: up to the signal scatter and the probe's work list (the end of a
+  // window's front stage), and from the probe to the packet (its back stage)
+  void run_join_front(int b, hipStream_t st, bool xchg);
+  void run_join_back(int b, int n_groups, bool with_labels, bool learn, hipStream_t st);
   // the window's span side (decode, partition, probe work list, span sort) on side_, forked
   // from `st` after the accumulators are reset and joined before the probe (one-GPU chain)
   void run_span_branch(int b, hipStream_t st);
@@ -229,9 +238,11 @@ class WindowEngine {
   // other GPUs' rows: per buffer, imported after this window's records; counts per buffer
   int n_rows_ = 0;                 // rows per generation = sig_cap + import_cap
   int gens_ = 1;                   // resident generations (1 + halo_windows with a halo)
+  int slots_ = 1;                  // physical generation slots: gens_, + 1 with overlapped windows
   int* rows_ = nullptr;            // device: rows of the current window
   unsigned long long* tmax_ = nullptr;
   GenMeta* gen_ = nullptr;         // device: generation slots, halo cut-offs, time ranges
+  const GenMeta* gen_prev_ = nullptr;  // the previous window's (another buffer's set, or gen_ itself)
   KeyTs* g_keys_ = nullptr;        // [gens][kKeyTypes * n_rows] partition list keys
   std::vector<SigRec*> imp_;
   uint32_t *remote_n_ = nullptr, *sel_cnt_ = nullptr, *sel_off_ = nullptr;
@@ -250,9 +261,38 @@ class WindowEngine {
   // span branch: a second compute stream, overlapping the span side of the chain (~50 us of
   // small kernels, plus the one-workgroup probe work list) with the signal side's decode and
   // scatter, joined before the probe: the one-GPU chain only (with the exchange the window runs
-  // as two graphs on the compute stream). On by default, off with MISLO_ONE_STREAM (the
-  // one-queue agent) or MISLO_SPAN_STREAM=0 (profiles/r5_probe/README.md).
+  // as two graphs on the compute stream). On by default in the serial chain, off with
+  // MISLO_ONE_STREAM (the one-queue agent), MISLO_SPAN_STREAM=0 (profiles/r5_probe/README.md) and,
+  // unless MISLO_SPAN_STREAM=1, with overlapped windows (profiles/window_overlap/README.md).
   hipStream_t side_ = nullptr;
+  // Window overlap (one-GPU chain only): a window runs as two stages, each a captured graph of
+  // its own -- the front stage (head load, accumulator reset, definitions, decode, span side,
+  // signal scatter, probe work list) on front_, the back stage (probe .. k_window_end) on
+  // compute_ -- so window k + 1's bandwidth-leaning front runs beside window k's latency-bound
+  // back. Front(k) waits for back(k - 2) (compute_done_), which bounds the overlap to one window;
+  // every array both stages touch is per buffer (BufSet) or per physical generation slot
+  // (slots_ = gens_ + 1): docs/ARCHITECTURE.md, "Window overlap". On where the span branch would
+  // be (not with MISLO_ONE_STREAM), never with the exchange or a communicator;
+  // MISLO_WINDOW_OVERLAP=0/1 overrides. The span branch is then off unless MISLO_SPAN_STREAM=1:
+  // three streams (copy, front, compute) and branch-free graphs keep one hardware queue each.
+  hipStream_t front_ = nullptr;
+  std::vector<hipEvent_t> front_done_;
+  bool overlap_ = false;
+  // The state both stages of a window touch, one set per buffer with overlapped windows (else
+  // one set): set_buffer(b) points the members of the same names at buffer b's set.
+  struct BufSet {
+    GenMeta* gen;
+    int* rows;
+    uint32_t *ring_state, *hist, *status, *confusion, *cnt, *gcnt;
+    unsigned long long *misc, *dbg, *top3, *gsum;
+    double *stats, *stats_count;
+    SpanRec* s_rec;
+    PartCodes* s_part;
+    uint32_t *s_items, *s_part_base, *probe_work;
+    PreSpan* s_pre;
+  };
+  std::vector<BufSet> sets_;
+  int set_of(int b) const { return sets_.size() > 1 ? b : 0; }
   hipEvent_t ev_fork_ = nullptr, ev_sigbase_ = nullptr, ev_spans_ = nullptr;
   bool branch_ = false;
   bool xspan_ = false;  // with the exchange: window head (part 4) and span side on side_ (part 3)

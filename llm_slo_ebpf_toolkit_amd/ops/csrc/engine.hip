@@ -165,27 +165,27 @@ void WindowEngine::alloc() {
     else copy2_ = copy_;
   }
   {
+    // Window overlap (engine.h): the front stage on a stream of its own. Not for an engine sized
+    // for the exchange (its windows run the two-part serial chain), and switched off by init_comm.
+    const char* v = getenv("MISLO_WINDOW_OVERLAP");
+    overlap_ = (v ? atoi(v) == 1 : !one_stream) && !one_stream && !(cfg_.xchg_cap > 0 && cfg_.import_cap > 0);
+    if (overlap_) HIPCHECK(hipStreamCreateWithFlags(&front_, hipStreamNonBlocking));
+    slots_ = gens_ + (overlap_ ? 1 : 0);
+  }
+  {
     // The span side of the chain (decode, partition, sort, the probe's work list) on a second
-    // stream, overlapping the signal side's decode: on by default where the streams have
-    // hardware queues to overlap on (not with MISLO_ONE_STREAM, the one-queue agent);
-    // MISLO_SPAN_STREAM=0/1 overrides. At the default priority it measured 0.521-0.526 against
-    // 0.539-0.546 ms per window (K = 100, profiles/r5_probe/README.md); a high-priority side
-    // stream (MISLO_SPAN_STREAM_PRIO=1, its own hardware-queue pool) measured 0.65.
+    // stream, overlapping the signal side's decode: on by default in the serial chain where the
+    // streams have hardware queues to overlap on (not with MISLO_ONE_STREAM, the one-queue
+    // agent); MISLO_SPAN_STREAM=0/1 overrides. At the default priority it measured 0.521-0.526
+    // against 0.539-0.546 ms per window (K = 100, profiles/r5_probe/README.md); a high-priority
+    // side stream (MISLO_SPAN_STREAM_PRIO=1, its own hardware-queue pool) measured 0.65.
+    // With overlapped windows it is off by default: the front stage is off the critical path,
+    // and a graph with a forked branch replays the branch on a stream of the runtime's own, so
+    // copy, front, compute, side and those no longer fit the four hardware queues one each --
+    // streams that share a queue wait for each other's copies and event waits. Measured 0.60
+    // with the branch against 0.48 ms per window without (profiles/window_overlap/README.md).
     const char* v = getenv("MISLO_SPAN_STREAM");
-    branch_ = v ? atoi(v) == 1 : !one_stream;
-    if (branch_) {
-      int lo = 0, hi = 0;
-      HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      const char* pv = getenv("MISLO_SPAN_STREAM_PRIO");  // 1 = the highest priority
-      if (pv && atoi(pv) == 1)
-        HIPCHECK(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
-      else
-        HIPCHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-      for (hipEvent_t* e : {&ev_fork_, &ev_sigbase_, &ev_spans_})
-        HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-      const char* xv = getenv("MISLO_XCHG_SPAN_SIDE");  // 0: the exchange path's span side in part 2
-      xspan_ = !(xv && atoi(xv) == 0);
-    }
+    if (v ? atoi(v) == 1 : (!one_stream && !overlap_)) enable_span_branch();
   }
   // one GPU: the window's tail (packet accumulate, timing) runs on the compute stream; a comm
   // stream of its own exists only with a communicator (init_comm). Every stream backs a
@@ -212,6 +212,7 @@ void WindowEngine::alloc() {
     head_done_.push_back(mk_event(false));
     compute_done_.push_back(mk_event(false));
     comm_done_.push_back(mk_event(false));
+    front_done_.push_back(mk_event(false));
     t_start_.push_back(mk_event(true));
     t_copy_end_.push_back(mk_event(true));
     t_comp0_.push_back(mk_event(true));
@@ -240,22 +241,45 @@ void WindowEngine::alloc() {
     std::memset(h, 0, kPodRows * 4);
     pod_host_ = static_cast<uint32_t*>(h);
   }
-  ring_state_ = dalloc<uint32_t>(kRsLen);
   trace_hash_ = dalloc<unsigned long long>(kTraceIdRows);
   HIPCHECK(hipMemset(trace_hash_, 0, (size_t)kTraceIdRows * 8));
   // other GPUs' trace rows and the selection of this GPU's; the generations' state
-  rows_ = dalloc<int>(16);
   tmax_ = dalloc<unsigned long long>(1);
   HIPCHECK(hipMemset(tmax_, 0, 8));
   remote_n_ = dalloc<uint32_t>(nb_);
   HIPCHECK(hipMemset(remote_n_, 0, nb_ * 4));
-  gen_ = dalloc<GenMeta>(1);
-  {
+  // the state both stages of a window touch: per buffer with overlapped windows, else one set
+  for (int i = 0; i < (overlap_ ? nb_ : 1); ++i) {
+    BufSet s{};
+    s.rows = dalloc<int>(16);
+    HIPCHECK(hipMemset(s.rows, 0, 16 * sizeof(int)));
+    s.ring_state = dalloc<uint32_t>(kRsLen);
+    s.gen = dalloc<GenMeta>(1);
     GenMeta g{};
-    g.cur = (uint32_t)gens_ - 1;  // the first window's k_gen_begin moves to slot 0
+    g.cur = (uint32_t)slots_ - 1;  // the first window's k_window_begin moves to slot 0
     for (int a = 0; a < kMaxGens; ++a) g.cut[a] = INT64_MAX;
-    HIPCHECK(hipMemcpy(gen_, &g, sizeof(g), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(s.gen, &g, sizeof(g), hipMemcpyHostToDevice));
+    s.s_part = dalloc<PartCodes>(S);
+    s.s_part_base = dalloc<uint32_t>(kKeyTypes * kParts + 1);
+    s.s_items = dalloc<uint32_t>(kKeyTypes * S);
+    s.s_pre = dalloc<PreSpan>((size_t)kKeyTypes * S);
+    s.s_rec = dalloc<SpanRec>(S);
+    s.probe_work = dalloc<uint32_t>(kProbeWorkLen);
+    HIPCHECK(hipMemset(s.probe_work, 0, kProbeWorkLen * 4));
+    s.top3 = dalloc<unsigned long long>(3 * S);
+    s.cnt = dalloc<uint32_t>(S);
+    s.gsum = dalloc<unsigned long long>((size_t)kGroupStripes * G * kSlots);
+    s.gcnt = dalloc<uint32_t>((size_t)kGroupStripes * G * kSlots);
+    s.hist = dalloc<uint32_t>(kSlots * kBuckets);
+    s.status = dalloc<uint32_t>(kSlots * 3);
+    s.misc = dalloc<unsigned long long>(kPacketMisc);
+    s.dbg = dalloc<unsigned long long>(kPacketDbg);
+    s.confusion = dalloc<uint32_t>(kMaxDomains * kMaxDomains);
+    s.stats = dalloc<double>(32 * 32);
+    s.stats_count = dalloc<double>(kMaxDomains);
+    sets_.push_back(s);
   }
+  set_buffer(0);
   sel_cnt_ = dalloc<uint32_t>(1024);
   sel_off_ = dalloc<uint32_t>(1024);
   for (int b = 0; b < nb_; ++b) imp_.push_back(cfg_.import_cap ? dalloc<SigRec>(cfg_.import_cap) : nullptr);
@@ -295,35 +319,21 @@ void WindowEngine::alloc() {
   g_part_off_ = dalloc<uint32_t>((size_t)(nblk_sig_ + nblk_imp_) * kKeyTypes * kParts);
   for (int b = 0; b < nb_; ++b) xchg_done_.push_back(mk_event(false));
   g_part_tot_ = dalloc<uint32_t>(kKeyTypes * kParts);
-  g_part_base_ = dalloc<uint32_t>((size_t)gens_ * kBaseLen);
-  // resident generations: rows, partition lists, list keys and offsets of the last gens_ windows
-  g_items_ = dalloc<uint32_t>((size_t)gens_ * kKeyTypes * N);
-  g_keys_ = dalloc<KeyTs>((size_t)gens_ * kKeyTypes * N);
-  g_rec_ = dalloc<SigRec>((size_t)gens_ * N);
-  s_part_ = dalloc<PartCodes>(S);
+  // resident generations: rows, partition lists, list keys and offsets of the last gens_ windows,
+  // over slots_ physical slots (one spare with overlapped windows: the next window's front stage
+  // decodes into it while this window's back stage still reads the other gens_)
+  g_part_base_ = dalloc<uint32_t>((size_t)slots_ * kBaseLen);
+  g_items_ = dalloc<uint32_t>((size_t)slots_ * kKeyTypes * N);
+  g_keys_ = dalloc<KeyTs>((size_t)slots_ * kKeyTypes * N);
+  g_rec_ = dalloc<SigRec>((size_t)slots_ * N);
+  // front-stage scratch (one window's front stage at a time, in stream order) and back-stage
+  // scratch (likewise) stay single
   s_part_blk_ = dalloc<uint32_t>((size_t)nblk_span_ * kKeyTypes * kParts);
   s_part_off_ = dalloc<uint32_t>((size_t)nblk_span_ * kKeyTypes * kParts);
   s_part_tot_ = dalloc<uint32_t>(kKeyTypes * kParts);
-  s_part_base_ = dalloc<uint32_t>(kKeyTypes * kParts + 1);
-  s_items_ = dalloc<uint32_t>(kKeyTypes * S);
-  s_pre_ = dalloc<PreSpan>((size_t)kKeyTypes * S);
-  s_rec_ = dalloc<SpanRec>(S);
-  probe_work_ = dalloc<uint32_t>(kProbeWorkLen);
-  HIPCHECK(hipMemset(probe_work_, 0, kProbeWorkLen * 4));
-  top3_ = dalloc<unsigned long long>(3 * S);
-  cnt_ = dalloc<uint32_t>(S);
   attrs_ = dalloc<float>(S * kSlots);
   conf_ = dalloc<float>(S);
   kernel_ms_ = dalloc<float>(S);
-  gsum_ = dalloc<unsigned long long>((size_t)kGroupStripes * G * kSlots);
-  gcnt_ = dalloc<uint32_t>((size_t)kGroupStripes * G * kSlots);
-  hist_ = dalloc<uint32_t>(kSlots * kBuckets);
-  status_ = dalloc<uint32_t>(kSlots * 3);
-  misc_ = dalloc<unsigned long long>(kPacketMisc);
-  dbg_ = dalloc<unsigned long long>(kPacketDbg);
-  confusion_ = dalloc<uint32_t>(kMaxDomains * kMaxDomains);
-  stats_ = dalloc<double>(32 * 32);
-  stats_count_ = dalloc<double>(kMaxDomains);
   HIPCHECK(hipDeviceSynchronize());
 }
 
@@ -352,24 +362,47 @@ WindowEngine::~WindowEngine() {
   for (auto p : in_dev_) hipFree(p);
   for (auto p : packet_dev_) hipFree(p);
   for (auto p : res_dev_) hipFree(p);
+  for (auto e : front_done_) hipEventDestroy(e);
+  for (const BufSet& s : sets_) {
+    void* per[] = {s.gen, s.rows, s.ring_state, s.hist, s.status, s.confusion, s.cnt, s.gcnt, s.misc, s.dbg, s.top3,
+                   s.gsum, s.stats, s.stats_count, s.s_rec, s.s_part, s.s_items, s.s_part_base, s.probe_work, s.s_pre};
+    for (void* p : per)
+      if (p) hipFree(p);
+  }
   void* bufs[] = {ctx_tab_, totals_, stats_acc_, p0_, model_dev_, g_status_, g_part_, g_part_blk_, g_part_off_,
-                  g_part_tot_, g_part_base_, g_items_, g_rec_, s_part_, s_part_blk_, s_part_off_, s_part_tot_,
-                  s_part_base_, s_items_, s_rec_, probe_work_, top3_, cnt_, attrs_, conf_, kernel_ms_, gsum_, gcnt_,
-                  hist_, status_, misc_, dbg_, confusion_, stats_, stats_count_, pod_sn_, ring_state_, trace_hash_,
-                  rows_, tmax_, remote_n_, sel_cnt_, sel_off_, sel_mask_, xsend_, xrecv_, g_keys_, gen_, s_pre_, app_dev_};
+                  g_part_tot_, g_part_base_, g_items_, g_rec_, s_part_blk_, s_part_off_, s_part_tot_,
+                  attrs_, conf_, kernel_ms_, pod_sn_, trace_hash_,
+                  tmax_, remote_n_, sel_cnt_, sel_off_, sel_mask_, xsend_, xrecv_, g_keys_, app_dev_};
   for (void* p : bufs)
     if (p) hipFree(p);
   if (copy_ && copy_ != compute_) hipStreamDestroy(copy_);
   if (copy2_ && copy2_ != copy_) hipStreamDestroy(copy2_);
   if (compute_) hipStreamDestroy(compute_);
   if (side_) hipStreamDestroy(side_);
+  if (front_) hipStreamDestroy(front_);
   for (hipEvent_t e : {ev_fork_, ev_sigbase_, ev_spans_})
     if (e) hipEventDestroy(e);
   if (comm_stream_ && comm_stream_ != compute_) hipStreamDestroy(comm_stream_);
 }
 
+void WindowEngine::enable_span_branch() {
+  if (branch_) return;
+  int lo = 0, hi = 0;
+  HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+  const char* pv = getenv("MISLO_SPAN_STREAM_PRIO");  // 1 = the highest priority
+  if (pv && atoi(pv) == 1)
+    HIPCHECK(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
+  else
+    HIPCHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
+  for (hipEvent_t* e : {&ev_fork_, &ev_sigbase_, &ev_spans_})
+    HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  const char* xv = getenv("MISLO_XCHG_SPAN_SIDE");  // 0: the exchange path's span side in part 2
+  xspan_ = !(xv && atoi(xv) == 0);
+  branch_ = true;
+}
+
 SignalCols WindowEngine::sig_cols() const {
-  return SignalCols{g_rec_, g_status_, g_part_, g_items_, g_keys_, g_part_base_, gen_, (int64_t)n_rows_, gens_};
+  return SignalCols{g_rec_, g_status_, g_part_, g_items_, g_keys_, g_part_base_, gen_, (int64_t)n_rows_, gens_, slots_};
 }
 SpanCols WindowEngine::span_cols() const { return SpanCols{s_rec_, s_part_}; }
 
@@ -433,9 +466,20 @@ void WindowEngine::wait_h2d(int64_t k) {
   HIPCHECK(hipEventSynchronize(h2d_part_[k % nb_]));
 }
 
-// This buffer's per-incident result pointers (read by the kernels the parts launch).
+// This buffer's per-incident result pointers and its set of the state both stages of a window
+// touch (read by the kernels the parts launch; every run_* starts here).
 void WindowEngine::set_buffer(int b) {
   const int G = cfg_.group_cap;
+  const BufSet& s = sets_[set_of(b)];
+  gen_ = s.gen;
+  gen_prev_ = sets_[set_of((b + nb_ - 1) % nb_)].gen;  // the previous window's buffer
+  rows_ = s.rows;
+  ring_state_ = s.ring_state;
+  hist_ = s.hist, status_ = s.status, confusion_ = s.confusion, cnt_ = s.cnt, gcnt_ = s.gcnt;
+  misc_ = s.misc, dbg_ = s.dbg, top3_ = s.top3, gsum_ = s.gsum;
+  stats_ = s.stats, stats_count_ = s.stats_count;
+  s_rec_ = s.s_rec, s_part_ = s.s_part, s_items_ = s.s_items, s_part_base_ = s.s_part_base;
+  probe_work_ = s.probe_work, s_pre_ = s.s_pre;
   uint8_t* r = res_dev_[b];  // this buffer's per-incident results block
   const size_t o_gconf = 16 * (size_t)G * 8, o_feat = o_gconf + (size_t)G * 8, o_pred = o_feat + 16 * (size_t)G * 4;
   const size_t o_ev = o_pred + (size_t)G * 4, o_sli = o_ev + 16 * (size_t)G * 4;
@@ -470,8 +514,8 @@ void WindowEngine::run_begin(int b, hipStream_t st) {
   add(sli_, (size_t)G * 6 * 4, 0);  // + the application retrieval counts (app_) and late breaches (late_)
   // + the next generation slot and the halo cut-offs (the finished window's tmax is read before
   // its reset), the ring state, no other GPUs' rows until merged, the window's rows
-  launch_window_begin(fl, gen_, tmax_, gens_, (long long)llround(cfg_.halo_ms * 1e6), ring_state_, remote_n_ + b,
-                      counts, n_rows_, rows_, st);
+  launch_window_begin(fl, gen_, gen_prev_, tmax_, gens_, slots_, (long long)llround(cfg_.halo_ms * 1e6), ring_state_,
+                      remote_n_ + b, counts, n_rows_, rows_, st);
 }
 
 // The captured part of a window: everything between the DMA and the packet.
@@ -508,10 +552,15 @@ void WindowEngine::run_part1(int b, hipStream_t st, bool xchg) {
 // Part 2: [the other GPUs' rows] -> partition -> spans -> join (this window's spans x every
 // generation's visible rows) -> posterior -> packet.
 void WindowEngine::run_part2(int b, int n_groups, bool with_labels, bool learn, hipStream_t st, bool xchg) {
+  run_join_front(b, st, xchg);
+  run_join_back(b, n_groups, with_labels, learn, st);
+}
+
+void WindowEngine::run_join_front(int b, hipStream_t st, bool xchg) {
+  set_buffer(b);
   uint8_t* in = in_dev_[b];
   const int* counts = reinterpret_cast<const int*>(in);
-  const int32_t* labels = reinterpret_cast<const int32_t*>(in + kHeadBytes);
-  const int N = n_rows_, S = cfg_.span_cap, G = cfg_.group_cap;
+  const int N = n_rows_;
   if (xchg) {
     const TraceIds tt{trace_hash_, kTraceIdRows};
     launch_decode_window(in + off_kern_, in + off_user_, counts, rows_, N, imp_[b], ctx_tab_, (int)kCtxRows, tt,
@@ -540,6 +589,14 @@ void WindowEngine::run_part2(int b, int n_groups, bool with_labels, bool learn, 
     HIPCHECK(hipEventRecord(ev_spans_, side_));
     HIPCHECK(hipStreamWaitEvent(st, ev_spans_, 0));  // spans sorted, work list built
   }
+}
+
+void WindowEngine::run_join_back(int b, int n_groups, bool with_labels, bool learn, hipStream_t st) {
+  set_buffer(b);
+  uint8_t* in = in_dev_[b];
+  const int* counts = reinterpret_cast<const int*>(in);
+  const int32_t* labels = reinterpret_cast<const int32_t*>(in + kHeadBytes);
+  const int S = cfg_.span_cap, G = cfg_.group_cap;
   launch_probe(span_cols(), s_items_, s_part_base_, sig_cols(), S, jp_, top3_, cnt_, n_groups, gsum_, gcnt_, dbg_,
                probe_work_, s_pre_, st);
   launch_finalize(counts + 1, S, top3_, cnt_, sig_cols(), span_cols(), jp_, nullptr, attrs_, conf_, kernel_ms_,
@@ -566,6 +623,7 @@ void WindowEngine::run_part2(int b, int n_groups, bool with_labels, bool learn, 
 // The span side of the chain: decode, partition, span sort (inputs: the span DMA and the reset
 // accumulators only).
 void WindowEngine::run_spans(int b, hipStream_t st) {
+  set_buffer(b);
   uint8_t* in = in_dev_[b];
   const int* counts = reinterpret_cast<const int*>(in);
   const int S = cfg_.span_cap, G = cfg_.group_cap;
@@ -599,13 +657,20 @@ void WindowEngine::launch_part(int part, int b, int n_groups, bool with_labels, 
       run_part2(b, n_groups, with_labels, learn, compute_, xchg);
     } else if (part == 3) {  // the exchange path's span side (xspan_)
       run_spans(b, side_);
-    } else {  // part 4: the exchange path's window head (xspan_)
+    } else if (part == 4) {  // the exchange path's window head (xspan_)
       run_begin(b, compute_);
+    } else if (part == 5) {  // overlapped windows: the front stage, on front_
+      run_part1(b, front_, false);
+      run_join_front(b, front_, false);
+    } else {  // part 6, overlapped windows: the back stage
+      run_join_back(b, n_groups, with_labels, learn, compute_);
     }
   };
-  hipStream_t cs = part == 3 ? side_ : compute_;  // the stream the part is captured on
+  hipStream_t cs = part == 3 ? side_ : part == 5 ? front_ : compute_;  // the stream the part is captured on
   if (!cfg_.use_graphs) return run();
-  auto key = std::make_tuple(b * 8 + part, n_groups, with_labels, learn);
+  // the front stage does not depend on the incident groups, the labels or the learning flag
+  auto key = part == 5 ? std::make_tuple(b * 8 + part, 0, false, false)
+                       : std::make_tuple(b * 8 + part, n_groups, with_labels, learn);
   auto it = graphs_.find(key);
   if (it == graphs_.end() && !warm_[b * 8 + part]) {
     run();
@@ -696,8 +761,15 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   HIPCHECK(hipEventRecord(t_copy_end_[b], copy2_));
   const auto te = std::chrono::steady_clock::now();
   dma_us_ += std::chrono::duration<double, std::micro>(te - td).count();
-  HIPCHECK(hipStreamWaitEvent(compute_, h2d_done_[b], 0));
-  HIPCHECK(hipStreamWaitEvent(compute_, h2d_part_[b], 0));
+  // the stream of the window's head and front half: front_ with overlapped windows (never with
+  // the exchange: overlap_ is off for an engine sized for it or holding a communicator)
+  hipStream_t fs = overlap_ ? front_ : compute_;
+  HIPCHECK(hipStreamWaitEvent(fs, h2d_done_[b], 0));
+  HIPCHECK(hipStreamWaitEvent(fs, h2d_part_[b], 0));
+  // overlapped: the front stage of window k starts once the back stage of window k - 2 ended. It
+  // overwrites the generation slot that stage probed as its oldest, and (two buffers) the buffer
+  // set and the head that stage read; with it at most one window's back stage runs beside a front.
+  if (overlap_ && k >= 2) HIPCHECK(hipStreamWaitEvent(fs, compute_done_[(k - 2) % nb_], 0));
   HIPCHECK(hipStreamWaitEvent(compute_, comm_done_[b], 0));  // packet b no longer reduced / read
   const bool injected = !inject_.empty();
   if (injected) {
@@ -707,13 +779,14 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
     HIPCHECK(hipMemcpyAsync(xrecv_, inject_.data(), inject_.size(), hipMemcpyHostToDevice, compute_));
     HIPCHECK(hipStreamSynchronize(compute_));
   }
-  HIPCHECK(hipEventRecord(t_comp0_[b], compute_));
+  HIPCHECK(hipEventRecord(t_comp0_[b], fs));
   // the head (counts, epoch bases, labels: < 1 KiB) by a kernel load from pinned host memory on
-  // the compute stream: a small hipMemcpyAsync H2D is written by the host through the BAR and
-  // blocks this thread, and a kernel on the copy stream put ~25 us of queue hand-offs between
-  // the window's DMAs (measured); the compute stream has the slack
-  to_host(head_host_[b], dst, off_kern_, compute_);
-  HIPCHECK(hipEventRecord(head_done_[b], compute_));
+  // the compute stream (the front stream with overlapped windows): a small hipMemcpyAsync H2D is
+  // written by the host through the BAR and blocks this thread, and a kernel on the copy stream
+  // put ~25 us of queue hand-offs between the window's DMAs (measured); the compute stream has
+  // the slack
+  to_host(head_host_[b], dst, off_kern_, fs);
+  HIPCHECK(hipEventRecord(head_done_[b], fs));
   if (cfg_.device_refit && k >= nb_) {
     // fold window k - nb's all-reduced statistics (packet b) and refit before window k: a
     // deterministic prequential lag of nb, identical on every rank
@@ -725,7 +798,14 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   const bool xchg = exchange() || injected;
   const auto tl = std::chrono::steady_clock::now();
   pre_us_ += std::chrono::duration<double, std::micro>(tl - te).count();
-  if (!xchg) {
+  if (overlap_) {
+    if (xchg) throw std::logic_error("the exchange path does not run with overlapped windows");
+    // two stages, two graphs: the front on front_, the back on compute_ once the front ended
+    launch_part(5, b, n_groups, with_labels, learn, false);
+    HIPCHECK(hipEventRecord(front_done_[b], front_));
+    HIPCHECK(hipStreamWaitEvent(compute_, front_done_[b], 0));
+    launch_part(6, b, n_groups, with_labels, learn, false);
+  } else if (!xchg) {
     launch_part(0, b, n_groups, with_labels, learn, false);
   } else {
     if (xspan_) {
@@ -924,11 +1004,14 @@ void WindowEngine::score_features(const float* feat, int n, const int32_t* label
 
 void WindowEngine::set_pods(const uint32_t* pods, const uint32_t* svcnode, size_t n) {
   // the host mirror is only written between the previous upload's completion (compute stream
-  // order: the upload precedes later windows) and this call; uploads are rare (pod churn)
-  HIPCHECK(hipStreamSynchronize(compute_));
+  // order: the upload precedes later windows) and this call; uploads are rare (pod churn). The
+  // table is read by the definitions and the decode: the front stage's stream with overlapped
+  // windows, so the upload takes effect at the next submitted window there as well.
+  hipStream_t st = overlap_ ? front_ : compute_;
+  HIPCHECK(hipStreamSynchronize(st));
   for (size_t i = 0; i < n; ++i)
     if (pods[i] < kPodRows) pod_host_[pods[i]] = svcnode[i];
-  HIPCHECK(hipMemcpyAsync(pod_sn_, pod_host_, kPodRows * 4, hipMemcpyHostToDevice, compute_));
+  HIPCHECK(hipMemcpyAsync(pod_sn_, pod_host_, kPodRows * 4, hipMemcpyHostToDevice, st));
 }
 
 std::vector<uint8_t> WindowEngine::sent_block() {
@@ -944,6 +1027,7 @@ std::vector<int64_t> WindowEngine::import_state() {
   unsigned long long tmax = 0;
   GenMeta g{};
   std::vector<uint32_t> r(nb_);
+  set_buffer(submitted_ ? (int)((submitted_ - 1) % nb_) : 0);  // the latest window's set
   HIPCHECK(hipMemcpy(rows, rows_, sizeof(rows), hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(&tmax, tmax_, 8, hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(&g, gen_, sizeof(g), hipMemcpyDeviceToHost));
@@ -952,7 +1036,7 @@ std::vector<int64_t> WindowEngine::import_state() {
   // buffer: other GPUs' rows
   std::vector<int64_t> out{rows[0], rows[1], (int64_t)tmax, gens_, g.cur, g.filled};
   for (int a = 0; a < kMaxGens; ++a) out.push_back(g.cut[a]);
-  for (int a = 0; a < kMaxGens; ++a) out.push_back(a < gens_ ? g.n_rows[(g.cur + gens_ - a) % gens_] : 0);
+  for (int a = 0; a < kMaxGens; ++a) out.push_back(a < gens_ ? g.n_rows[(g.cur + slots_ - a) % slots_] : 0);
   for (int b = 0; b < nb_; ++b) out.push_back(r[b]);
   return out;
 }
@@ -986,6 +1070,12 @@ void WindowEngine::init_comm(const ncclUniqueId& id, int rank, int world) {
   if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("communicator rank / world");
   if (submitted_) throw std::logic_error("init_comm before the first window");
   HIPCHECK(hipSetDevice(cfg_.device));
+  if (overlap_) {  // the windows of an engine with a communicator run the serial chain on compute_
+    HIPCHECK(hipStreamSynchronize(front_));  // a pod table upload queued there
+    overlap_ = false;
+    // the serial chain's default again: the span side on its own stream
+    if (!getenv("MISLO_SPAN_STREAM")) enable_span_branch();
+  }
   NCCLCHECK(ncclCommInitRank(&comm_, world, id, rank));
   {
     // the comm stream at its own priority: streams of one priority share that priority's
@@ -1071,6 +1161,7 @@ void WindowEngine::model_bytes(void* out) {
 void WindowEngine::sync() {
   HIPCHECK(hipStreamSynchronize(copy_));
   if (copy2_ != copy_) HIPCHECK(hipStreamSynchronize(copy2_));
+  if (front_) HIPCHECK(hipStreamSynchronize(front_));  // the front stages (and a pod table upload)
   HIPCHECK(hipStreamSynchronize(compute_));
   HIPCHECK(hipStreamSynchronize(comm_stream_));
 }

@@ -231,11 +231,14 @@ __global__ void k_window_rows(const int* __restrict__ counts, const uint32_t* __
 // slot (its old rows, kMaxGens windows back, drop out), and the visibility cut-off of every
 // age: a row of window k - a stays visible in window k while ts >= tmax_i - halo for every
 // window i in [k - a, k - 1] (a window without local records ends the chain, as an empty
-// selection would).
-__device__ __forceinline__ void gen_begin_body(GenMeta* __restrict__ g, unsigned long long tmax_prev, int gens,
-                                               long long halo_ns) {
+// selection would). The generations rotate over `slots` physical slots (>= gens: one spare with
+// overlapped windows); `prev` is the previous window's state when each buffer keeps its own copy
+// (the previous window's back half may still be reading it), else g itself.
+__device__ __forceinline__ void gen_begin_body(GenMeta* g, const GenMeta* prev, unsigned long long tmax_prev, int gens,
+                                               int slots, long long halo_ns) {
+  if (prev != g) *g = *prev;
   if (g->filled > 0) g->tmax_local[g->cur] = (int64_t)tmax_prev;
-  const uint32_t cur = (g->cur + 1) % (uint32_t)gens;
+  const uint32_t cur = (g->cur + 1) % (uint32_t)slots;
   g->cur = cur;
   g->filled = min(g->filled + 1, (uint32_t)gens);
   g->n_local[cur] = 0;
@@ -250,7 +253,7 @@ __device__ __forceinline__ void gen_begin_body(GenMeta* __restrict__ g, unsigned
   int64_t c = INT64_MIN;
   for (int a = 1; a < kMaxGens; ++a) {
     if (ok && a < gens && (uint32_t)a < g->filled) {
-      const int64_t tm = g->tmax_local[(cur + (uint32_t)(gens - a)) % (uint32_t)gens];
+      const int64_t tm = g->tmax_local[(cur + (uint32_t)(slots - a)) % (uint32_t)slots];
       if (tm == 0) ok = false;
       else c = max(c, tm - (int64_t)halo_ns);
     } else {
@@ -265,8 +268,9 @@ __device__ __forceinline__ void gen_begin_body(GenMeta* __restrict__ g, unsigned
 // the accumulators while thread 0 of block 0 runs the ordered scalar part -- the finished
 // window's tmax into its generation, then tmax reset; the ring state (first busy record: none);
 // no other GPUs' rows yet; the window's row counts.
-__global__ __launch_bounds__(256) void k_window_begin(FillList fl, GenMeta* __restrict__ gen,
-                                                      unsigned long long* __restrict__ tmax, int gens, long long halo_ns,
+__global__ __launch_bounds__(256) void k_window_begin(FillList fl, GenMeta* gen, const GenMeta* gen_prev,
+                                                      unsigned long long* __restrict__ tmax, int gens, int slots,
+                                                      long long halo_ns,
                                                       uint32_t* __restrict__ ring_state, uint32_t* __restrict__ remote_n,
                                                       const int* __restrict__ counts, int cap, int* __restrict__ rows) {
   for (int q = 0; q < fl.count; ++q) {
@@ -274,7 +278,7 @@ __global__ __launch_bounds__(256) void k_window_begin(FillList fl, GenMeta* __re
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < sg.n; i += gridDim.x * 256) sg.ptr[i] = sg.value;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (gen) gen_begin_body(gen, *tmax, gens, halo_ns);
+    if (gen) gen_begin_body(gen, gen_prev ? gen_prev : gen, *tmax, gens, slots, halo_ns);
     *tmax = 0ull;
     ring_state[kRsFirstBusy] = 0xFFFFFFFFu;
     for (int j = 1; j < kRsLen; ++j) ring_state[j] = 0u;
@@ -322,11 +326,11 @@ void launch_window_rows(const int* counts, const uint32_t* remote_n, int cap, in
   hipLaunchKernelGGL(k_window_rows, dim3(1), dim3(64), 0, stream, counts, remote_n, cap, rows, gen);
 }
 
-void launch_window_begin(const FillList& fl, GenMeta* gen, unsigned long long* tmax, int gens, long long halo_ns,
-                         uint32_t* ring_state, uint32_t* remote_n, const int* counts, int cap, int* rows,
-                         hipStream_t stream) {
-  hipLaunchKernelGGL(k_window_begin, dim3(256), dim3(256), 0, stream, fl, gen, tmax, gens, halo_ns, ring_state,
-                     remote_n, counts, cap, rows);
+void launch_window_begin(const FillList& fl, GenMeta* gen, const GenMeta* gen_prev, unsigned long long* tmax, int gens,
+                         int slots, long long halo_ns, uint32_t* ring_state, uint32_t* remote_n, const int* counts,
+                         int cap, int* rows, hipStream_t stream) {
+  hipLaunchKernelGGL(k_window_begin, dim3(256), dim3(256), 0, stream, fl, gen, gen_prev, tmax, gens, slots, halo_ns,
+                     ring_state, remote_n, counts, cap, rows);
 }
 
 }  // namespace mislo

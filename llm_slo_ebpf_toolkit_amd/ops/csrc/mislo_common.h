@@ -184,13 +184,17 @@ struct alignas(16) KeyTs {
 // re-partitioning them (engine.hip k_gen_begin). Generation slots rotate; everything here is
 // device state, so a captured window graph replays against whichever slot is current.
 constexpr int kMaxGens = 4;  // this window + up to 3 earlier ones (the top-3 key holds the age in 2 bits)
+// Physical slots: one more than the generations when two windows overlap (engine.h, window
+// overlap): the next window's front half decodes into the slot that is NOT among the gens slots
+// the running window's probe and finalize still read. Ages stay logical (0 .. gens - 1).
+constexpr int kMaxSlots = kMaxGens + 1;
 struct GenMeta {
   uint32_t cur;                    // slot of the window being processed
   uint32_t filled;                 // windows held, this one included (<= gens)
-  uint32_t n_local[kMaxGens];      // per slot: node-local rows (the other GPUs' rows follow them)
-  uint32_t n_rows[kMaxGens];       // per slot: rows
-  int64_t tmax_local[kMaxGens];    // per slot: latest local joinable timestamp (the halo anchor; 0 = none)
-  uint64_t tlo[kMaxGens], thi[kMaxGens];  // per slot: joinable row time range (order-preserving u64 image)
+  uint32_t n_local[kMaxSlots];     // per slot: node-local rows (the other GPUs' rows follow them)
+  uint32_t n_rows[kMaxSlots];      // per slot: rows
+  int64_t tmax_local[kMaxSlots];   // per slot: latest local joinable timestamp (the halo anchor; 0 = none)
+  uint64_t tlo[kMaxSlots], thi[kMaxSlots];  // per slot: joinable row time range (order-preserving u64 image)
   int64_t cut[kMaxGens];           // per age: visible rows have ts >= cut (INT64_MAX: none visible)
   uint64_t span_lo, span_hi;       // this window's joinable spans (u64 image)
 };
@@ -199,20 +203,22 @@ __host__ __device__ inline uint64_t ts_image(int64_t t) { return (uint64_t)t ^ 0
 __host__ __device__ inline int64_t ts_of_image(uint64_t u) { return (int64_t)(u ^ 0x8000000000000000ull); }
 
 struct SignalCols {
-  SigRec* rec;          // [gens][stride] row records
+  SigRec* rec;          // [slots][stride] row records
   uint8_t* status;      // this window's rows: 0 ok, 1 warning, 2 error
   PartCodes* part;      // this window's rows
-  uint32_t* items = nullptr;  // [gens][kKeyTypes * stride] partition lists (row indices)
-  KeyTs* keys = nullptr;      // [gens][kKeyTypes * stride] the lists' (key hash, ts)
-  uint32_t* base = nullptr;   // [gens][kKeyTypes * kParts + 1] list offsets
+  uint32_t* items = nullptr;  // [slots][kKeyTypes * stride] partition lists (row indices)
+  KeyTs* keys = nullptr;      // [slots][kKeyTypes * stride] the lists' (key hash, ts)
+  uint32_t* base = nullptr;   // [slots][kKeyTypes * kParts + 1] list offsets
   GenMeta* gen = nullptr;     // nullptr: one generation (slot 0)
   int64_t stride = 0;         // rows per generation
-  int gens = 1;
+  int gens = 1;               // logical generations: the ages a window joins (row classes, cut-offs)
+  int slots = 0;              // physical slots the generations rotate over (0: = gens)
 };
 constexpr int kBaseLen = kKeyTypes * kParts + 1;  // list offsets per generation
 __device__ __forceinline__ uint32_t cur_slot(const SignalCols& c) { return c.gen ? c.gen->cur : 0u; }
 __device__ __forceinline__ uint32_t age_slot(const SignalCols& c, uint32_t cur, int age) {
-  return (cur + (uint32_t)(c.gens - age)) % (uint32_t)c.gens;
+  const uint32_t n = (uint32_t)(c.slots > 0 ? c.slots : c.gens);
+  return (cur + n - (uint32_t)age) % n;
 }
 
 struct SpanCols {

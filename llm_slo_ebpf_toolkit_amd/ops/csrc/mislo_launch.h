@@ -131,10 +131,12 @@ void launch_window_rows(const int* counts, const uint32_t* remote_n, int cap, in
                         hipStream_t stream);
 // head of a window's graph: the next generation slot and the halo's per-age visibility cut-offs,
 // tmax / ring state / other GPUs' row count reset, the window's row counts, and the fills of
-// `fl` (see exchange.hip)
-void launch_window_begin(const FillList& fl, GenMeta* gen, unsigned long long* tmax, int gens, long long halo_ns,
-                         uint32_t* ring_state, uint32_t* remote_n, const int* counts, int cap, int* rows,
-                         hipStream_t stream);
+// `fl` (see exchange.hip). gen_prev: the previous window's generation state, copied into `gen`
+// first (per-buffer copies; nullptr or gen itself: one copy stepped in place); slots: the
+// physical slots the gens generations rotate over
+void launch_window_begin(const FillList& fl, GenMeta* gen, const GenMeta* gen_prev, unsigned long long* tmax, int gens,
+                         int slots, long long halo_ns, uint32_t* ring_state, uint32_t* remote_n, const int* counts,
+                         int cap, int* rows, hipStream_t stream);
 
 // join.hip
 // rows [0, n_dev[0]) decoded by nblk blocks; with split (nblk_a < nblk) the first nblk_a blocks
