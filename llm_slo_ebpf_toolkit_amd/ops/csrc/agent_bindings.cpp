@@ -126,23 +126,11 @@ class PyEngine {
   py::list results_all(int64_t k, int n_groups) {
     WindowEngine& e = eng();
     if (n_groups < 0 || n_groups > e.config().group_cap) throw std::invalid_argument("n_groups");
-    const size_t G = e.config().group_cap, bytes = e.result_bytes();
+    const ResultLayout lay = e.layout();
     const uint8_t* base = e.results_all(k);
-    const size_t o_gconf = 16 * G * 8, o_feat = o_gconf + G * 8, o_pred = o_feat + 16 * G * 4, o_ev = o_pred + G * 4;
-    const size_t o_sli = o_ev + 16 * G * 4;
     py::list out;
     const int w = e.has_comm() ? e.world() : 1;
-    for (int r = 0; r < w; ++r) {
-      const uint8_t* p = base + (size_t)r * bytes;
-      out.append(result_dict(ResultView{reinterpret_cast<const double*>(p), reinterpret_cast<const double*>(p + o_gconf),
-                                        reinterpret_cast<const float*>(p + o_feat),
-                                        reinterpret_cast<const int32_t*>(p + o_pred),
-                                        reinterpret_cast<const uint32_t*>(p + o_ev),
-                                        reinterpret_cast<const uint32_t*>(p + o_sli),
-                                        reinterpret_cast<const uint32_t*>(p + o_sli) + 2 * G,
-                                        reinterpret_cast<const uint32_t*>(p + o_sli) + 4 * G},
-                             n_groups));
-    }
+    for (int r = 0; r < w; ++r) out.append(result_dict(lay.view(base + (size_t)r * lay.bytes()), n_groups));
     return out;
   }
   static py::dict result_dict(const ResultView& r, int n_groups) {

@@ -22,14 +22,17 @@
 // where their own window decoded and partitioned them -- and the other GPUs' trace-tagged rows of
 // window k (exchange.hip), so joins across window and GPU boundaries match.
 //
+// The streams run side by side, so the DMA of window k+1 and the node-wide all-reduce of window k
+// run under the kernels of window k+1. The whole compute chain of a buffer is captured once into
+// a HIP graph and replayed (one launch per window). Host waits use blocking-sync events (no
+// spin: the agent's CPU budget, REF pkg/safety/overhead_guard.go:77-107, counts this process).
+//
 // One GPU without the exchange: the graph is split at the probe into a front stage on a front
 // stream and a back stage on the compute stream, and window k+1's front runs beside window k's
 // back (window overlap, below at front_).
 //
-// so the DMA of window k+1 and the node-wide all-reduce of window k run under the kernels of
-// window k+1. The whole compute chain of a buffer is captured once into a HIP graph and
-// replayed (one launch per window). Host waits use blocking-sync events (no spin: the
-// agent's CPU budget, REF pkg/safety/overhead_guard.go:77-107, counts this process).
+// Everything indexed by b is one record (Buf), built by alloc() / init_comm() and never
+// re-pointed; every run_* is handed the buffer it works on.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,6 +40,7 @@
 
 #include <map>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "mislo_launch.h"
@@ -85,16 +89,41 @@ struct EngineConfig {
   bool split_rings = false;
 };
 
-// per-incident results of a window, in one pinned block (one D2H)
-struct ResultView {
-  const double* post;     // [G][16]
-  const double* gconf;    // [G]
-  const float* feat;      // [G][16]
-  const int32_t* pred;    // [G]
-  const uint32_t* evbits; // [G][16]
-  const uint32_t* sli;    // [G][2]: spans, TTFT-SLO breaches
-  const uint32_t* app;    // [G][2]: spans with an application retrieval time, its sum (10 us units)
-  const uint32_t* late;   // [G][2]: breaches of earlier windows reported in this one (SpanMap::grp_late), spare
+// per-incident results of a window, in one block (one D2H): views into a block of `Byte`s (the
+// device block the kernels write, or a const pinned host block)
+template <class Byte>
+struct ResultViewT {
+  template <class T>
+  using P = std::conditional_t<std::is_const_v<Byte>, const T, T>*;
+  P<double> post;     // [G][16]
+  P<double> gconf;    // [G]
+  P<float> feat;      // [G][16]
+  P<int32_t> pred;    // [G]
+  P<uint32_t> evbits; // [G][16]
+  P<uint32_t> sli;    // [G][2]: spans, TTFT-SLO breaches
+  P<uint32_t> app;    // [G][2]: spans with an application retrieval time, its sum (10 us units)
+  P<uint32_t> late;   // [G][2]: breaches of earlier windows reported in this one (SpanMap::grp_late), spare
+};
+using ResultView = ResultViewT<const uint8_t>;
+
+// The block's byte layout for G incident groups, columns in ResultViewT's order (sli, app and
+// late are adjacent: one fill resets the three)
+struct ResultLayout {
+  size_t G;
+  size_t gconf() const { return 16 * G * 8; }
+  size_t feat() const { return gconf() + G * 8; }
+  size_t pred() const { return feat() + 16 * G * 4; }
+  size_t evbits() const { return pred() + G * 4; }
+  size_t sli() const { return evbits() + 16 * G * 4; }
+  size_t bytes() const { return sli() + 6 * G * 4; }
+  template <class Byte>
+  ResultViewT<Byte> view(Byte* r) const {
+    ResultViewT<Byte> v;
+    auto set = [r](auto& p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(r + off); };
+    set(v.post, 0), set(v.gconf, gconf()), set(v.feat, feat()), set(v.pred, pred()), set(v.evbits, evbits());
+    set(v.sli, sli()), set(v.app, sli() + 2 * G * 4), set(v.late, sli() + 4 * G * 4);
+    return v;
+  }
 };
 
 // The window's inputs: ring byte ranges (as the rings hold them) and the window metadata.
@@ -128,8 +157,9 @@ class WindowEngine {
   void wait_h2d(int64_t k);
   bool query(int64_t k);      // window k's results are in host memory
   void wait(int64_t k);
-  const double* packet(int64_t k) const { return packet_host_[k % nb_]; }
-  ResultView results(int64_t k) const;
+  const double* packet(int64_t k) const { return bufs_[k % nb_].packet_host; }
+  ResultView results(int64_t k) const { return layout().view<const uint8_t>(bufs_[k % nb_].res_host); }
+  ResultLayout layout() const { return ResultLayout{(size_t)cfg_.group_cap}; }
   // device time of window k (ms): DMA start -> results in host memory, and the compute stream's share
   std::pair<float, float> window_ms(int64_t k);
   std::vector<float> copy_ms(int64_t k);  // window k's DMA time and the copy stream's idle gap before it
@@ -158,7 +188,6 @@ class WindowEngine {
   // other GPUs' rows for the next window, as their exchange blocks would arrive over RCCL (world
   // blocks of [24-byte header: uint32 row count | XRec rows], this rank's block skipped); the
   // next submit runs the exchange path (decode part 1, merge, part 2) with them
-
   void inject_remote(const void* blocks, size_t stride, int world, int me);
   void set_join_params(double window_ms, double threshold, int fanout, int group_mode);
   void init_comm(const ncclUniqueId& id, int rank, int world);
@@ -167,8 +196,8 @@ class WindowEngine {
   int world() const { return world_; }
   // all ranks' per-incident results of window k ([world] blocks of result_bytes(); this rank's
   // alone without a communicator)
-  const uint8_t* results_all(int64_t k) const { return comm_ ? res_all_host_[k % nb_] : res_host_[k % nb_]; }
-  size_t result_bytes() const { return res_bytes_; }
+  const uint8_t* results_all(int64_t k) const { return comm_ ? bufs_[k % nb_].res_all_host : bufs_[k % nb_].res_host; }
+  size_t result_bytes() const { return layout().bytes(); }
 
   void totals(double* out);           // accumulated (all-reduced) packets (synchronous)
   void reset_totals();
@@ -201,26 +230,47 @@ class WindowEngine {
   // the record ownership filter's (rank, world): none with split rings (EngineConfig::split_rings)
   int rec_shard_rank() const { return cfg_.split_rings ? 0 : cfg_.shard_rank; }
   int rec_shard_world() const { return cfg_.split_rings ? 1 : cfg_.shard_world; }
+  struct Buf;
+  // The parts a window's chain is launched (and captured) in. One GPU: the whole window, or with
+  // overlapped windows its front and back stage. With the exchange: the records (part 1), the
+  // exchange, the join (part 2), and with xspan_ the window head and the span side on their own.
+  enum class Stage : int { Window, Records, Join, XchgSpans, XchgHead, Front, Back };
+  static constexpr int kStageSlots = 8;  // graph key and warm_ index: b * kStageSlots + stage
   void alloc();
   void enable_span_branch();  // side_, its events, branch_ (alloc; init_comm leaving the overlap)
-  void set_buffer(int b);
-  void run_begin(int b, hipStream_t st);
-  void run_part1(int b, hipStream_t st, bool xchg);
-  void run_part2(int b, int n_groups, bool with_labels, bool learn, hipStream_t st, bool xchg);
-  // run_part2's two halves: up to the signal scatter and the probe's work list (the end of a
+  void run_begin(const Buf& buf, hipStream_t st);
+  void run_part1(const Buf& buf, hipStream_t st, bool xchg);
+  // part 2's two halves: up to the signal scatter and the probe's work list (the end of a
   // window's front stage), and from the probe to the packet (its back stage)
-  void run_join_front(int b, hipStream_t st, bool xchg);
-  void run_join_back(int b, int n_groups, bool with_labels, bool learn, hipStream_t st);
+  void run_join_front(const Buf& buf, hipStream_t st, bool xchg);
+  void run_join_back(const Buf& buf, int n_groups, bool with_labels, bool learn, hipStream_t st);
   // the window's span side (decode, partition, probe work list, span sort) on side_, forked
   // from `st` after the accumulators are reset and joined before the probe (one-GPU chain)
-  void run_span_branch(int b, hipStream_t st);
-  void run_spans(int b, hipStream_t st);
-  void launch_part(int part, int b, int n_groups, bool with_labels, bool learn, bool xchg);
-  SignalCols sig_cols() const;
-  SpanCols span_cols() const;
+  void run_span_branch(const Buf& buf, hipStream_t st);
+  void run_spans(const Buf& buf, hipStream_t st);
+  void launch_part(Stage part, const Buf& buf, int n_groups, bool with_labels, bool learn);
+  // the other GPUs' rows of this window (exchange blocks) into the buffer's imports, then its rows
+  void merge_remote(const Buf& buf, const uint8_t* blocks, size_t stride, int world, int me, hipStream_t st);
+  void refit(const double* add);  // fold `add` (or nothing) into the statistics and refit the model
+  SignalCols sig_cols(const Buf& buf) const;
+  SpanCols span_cols(const Buf& buf) const;
   bool registered(const void* p, size_t n) const;
   size_t dma(const std::vector<Seg>& segs, uint8_t* dst, size_t cap, uint8_t*& staging, size_t& st_off,
              hipStream_t st);
+  // What the engine created; destroyed after the graphs and the communicators, in this order
+  struct Owner {
+    std::vector<hipEvent_t> events;
+    std::vector<void*> dev, host;
+    std::vector<hipStream_t> streams;
+    void free_dev(void* p);  // a block released early: scratch, an outgrown xrecv_
+    ~Owner();
+  } own_;
+  template <class T>
+  T* dalloc(size_t n, bool zero = false);
+  void* host_alloc(size_t bytes, unsigned flags);
+  void* host_block(size_t bytes);  // zeroed, device-visible: the kernels store into it
+  hipEvent_t mk_event(unsigned flags);
+  hipStream_t mk_stream(bool high_priority = false);
 
   EngineConfig cfg_;
   int nb_, max_ahead_;
@@ -229,23 +279,15 @@ class WindowEngine {
   size_t kern_bytes() const { return (size_t)kRecStride * (((size_t)cfg_.sig_cap + kBatchSlots - 1) / kBatchSlots); }
   std::vector<std::pair<const uint8_t*, size_t>> registered_;
   size_t staged_bytes_ = 0, direct_bytes_ = 0;
-  uint32_t *pod_sn_ = nullptr, *pod_host_ = nullptr, *ring_state_ = nullptr;
+  uint32_t *pod_sn_ = nullptr, *pod_host_ = nullptr;
   unsigned long long* trace_hash_ = nullptr;  // kernel trace id -> hash
-  uint32_t* sli_ = nullptr;
-  uint32_t* app_ = nullptr;         // this buffer's [G][2] application retrieval counts (after sli_)
-  uint32_t* late_ = nullptr;        // this buffer's [G][2] late breaches (after app_)
   AppModel* app_dev_ = nullptr;     // the application evidence model (device)
-  // other GPUs' rows: per buffer, imported after this window's records; counts per buffer
   int n_rows_ = 0;                 // rows per generation = sig_cap + import_cap
   int gens_ = 1;                   // resident generations (1 + halo_windows with a halo)
   int slots_ = 1;                  // physical generation slots: gens_, + 1 with overlapped windows
-  int* rows_ = nullptr;            // device: rows of the current window
   unsigned long long* tmax_ = nullptr;
-  GenMeta* gen_ = nullptr;         // device: generation slots, halo cut-offs, time ranges
-  const GenMeta* gen_prev_ = nullptr;  // the previous window's (another buffer's set, or gen_ itself)
   KeyTs* g_keys_ = nullptr;        // [gens][kKeyTypes * n_rows] partition list keys
-  std::vector<SigRec*> imp_;
-  uint32_t *remote_n_ = nullptr, *sel_cnt_ = nullptr, *sel_off_ = nullptr;
+  uint32_t *remote_n_ = nullptr, *sel_cnt_ = nullptr, *sel_off_ = nullptr;  // remote_n_: [nb], Buf::remote_n
   unsigned long long* sel_mask_ = nullptr;  // the fused selection's ballot masks (nullptr: two passes)
   int sel_stride_ = 0;
   uint8_t *xsend_ = nullptr, *xrecv_ = nullptr;
@@ -256,8 +298,6 @@ class WindowEngine {
   size_t inject_stride_ = 0;
   int inject_world_ = 0, inject_me_ = 0;
   int rank_ = 0, world_ = 1;
-  std::vector<uint8_t*> res_all_dev_, res_all_host_;
-  std::vector<hipEvent_t> xchg_done_;
   // span branch: a second compute stream, overlapping the span side of the chain (~50 us of
   // small kernels, plus the one-workgroup probe work list) with the signal side's decode and
   // scatter, joined before the probe: the one-GPU chain only (with the exchange the window runs
@@ -269,47 +309,58 @@ class WindowEngine {
   // its own -- the front stage (head load, accumulator reset, definitions, decode, span side,
   // signal scatter, probe work list) on front_, the back stage (probe .. k_window_end) on
   // compute_ -- so window k + 1's bandwidth-leaning front runs beside window k's latency-bound
-  // back. Front(k) waits for back(k - 2) (compute_done_), which bounds the overlap to one window;
+  // back. Front(k) waits for back(k - 2) (compute_done), which bounds the overlap to one window;
   // every array both stages touch is per buffer (BufSet) or per physical generation slot
   // (slots_ = gens_ + 1): docs/ARCHITECTURE.md, "Window overlap". On where the span branch would
   // be (not with MISLO_ONE_STREAM), never with the exchange or a communicator;
   // MISLO_WINDOW_OVERLAP=0/1 overrides. The span branch is then off unless MISLO_SPAN_STREAM=1:
   // three streams (copy, front, compute) and branch-free graphs keep one hardware queue each.
   hipStream_t front_ = nullptr;
-  std::vector<hipEvent_t> front_done_;
   bool overlap_ = false;
   // The state both stages of a window touch, one set per buffer with overlapped windows (else
-  // one set): set_buffer(b) points the members of the same names at buffer b's set.
+  // one set, shared by every buffer): reached through Buf::set.
   struct BufSet {
-    GenMeta* gen;
-    int* rows;
+    GenMeta* gen;  // generation slots, halo cut-offs, time ranges
+    int* rows;     // rows of the window
     uint32_t *ring_state, *hist, *status, *confusion, *cnt, *gcnt;
     unsigned long long *misc, *dbg, *top3, *gsum;
     double *stats, *stats_count;
     SpanRec* s_rec;
     PartCodes* s_part;
     uint32_t *s_items, *s_part_base, *probe_work;
-    PreSpan* s_pre;
+    PreSpan* s_pre;  // the probe's per-window sorted span lists (k_span_sort)
   };
   std::vector<BufSet> sets_;
-  int set_of(int b) const { return sets_.size() > 1 ? b : 0; }
+  // Everything of buffer b (window k uses b = k % nb). Built by alloc(), the res_all blocks by
+  // init_comm(); afterwards only `staging` changes, once, on the first unregistered range.
+  struct Buf {
+    int b;
+    uint8_t* in;         // device: [head | framed | user | spans]
+    uint8_t* head_host;  // pinned: counts + labels
+    uint8_t* staging;    // pinned staging for unregistered ranges (allocated on first use)
+    double *packet_dev, *packet_host;
+    uint8_t *res_dev, *res_host;          // per-incident results block and its pinned copy
+    uint8_t *res_all_dev, *res_all_host;  // every rank's (with a communicator)
+    ResultViewT<uint8_t> res;             // views into res_dev
+    SigRec* imp;                          // other GPUs' rows, imported after this window's records
+    uint32_t* remote_n;                   // their count
+    const BufSet* set;
+    const GenMeta* gen_prev;  // the previous window's: buffer b - 1's set (or this one's own)
+    hipEvent_t h2d_done, h2d_part, head_done, front_done, compute_done, comm_done, xchg_done;
+    hipEvent_t t_start, t_copy_end, t_comp0, t_comp1, t_end;
+    const int* counts() const { return reinterpret_cast<const int*>(in); }
+  };
+  std::vector<Buf> bufs_;
   hipEvent_t ev_fork_ = nullptr, ev_sigbase_ = nullptr, ev_spans_ = nullptr;
   bool branch_ = false;
-  bool xspan_ = false;  // with the exchange: window head (part 4) and span side on side_ (part 3)
+  bool xspan_ = false;  // with the exchange: Stage::XchgHead, and Stage::XchgSpans on side_
   bool exchange() const { return comm_ && cfg_.xchg_cap > 0 && cfg_.import_cap > 0; }
   JoinParams jp_{};
   int nblk_sig_ = 1, nblk_span_ = 1;
   hipStream_t copy_ = nullptr, copy2_ = nullptr, compute_ = nullptr, comm_stream_ = nullptr;
   ncclComm_t comm_ = nullptr;
   ncclComm_t xcomm_ = nullptr;  // the trace-row exchange's communicator (compute stream; init_comm)
-  // device buffers
-  std::vector<uint8_t*> in_dev_;     // per buffer: [head | framed | user | spans]
-  std::vector<uint8_t*> head_host_;  // per buffer: counts + labels (pinned)
-  std::vector<uint8_t*> staging_;    // per buffer: pinned staging for unregistered ranges
-  std::vector<double*> packet_dev_;
-  std::vector<double*> packet_host_;
-  std::vector<uint8_t*> res_dev_, res_host_;  // per buffer
-  size_t res_bytes_ = 0;
+  // device buffers shared by every window
   uint32_t* ctx_tab_ = nullptr;
   double *totals_ = nullptr, *stats_acc_ = nullptr, *p0_ = nullptr;
   uint8_t* model_dev_ = nullptr;
@@ -320,27 +371,8 @@ class WindowEngine {
   uint32_t *g_part_blk_ = nullptr, *g_part_off_ = nullptr, *g_part_tot_ = nullptr, *g_part_base_ = nullptr,
            *g_items_ = nullptr;
   SigRec* g_rec_ = nullptr;
-  PartCodes* s_part_ = nullptr;
-  uint32_t *s_part_blk_ = nullptr, *s_part_off_ = nullptr, *s_part_tot_ = nullptr, *s_part_base_ = nullptr,
-           *s_items_ = nullptr, *probe_work_ = nullptr;
-  PreSpan* s_pre_ = nullptr;  // the probe's per-window sorted span lists (k_span_sort)
-  SpanRec* s_rec_ = nullptr;
-  unsigned long long* top3_ = nullptr;
-  uint32_t* cnt_ = nullptr;
+  uint32_t *s_part_blk_ = nullptr, *s_part_off_ = nullptr, *s_part_tot_ = nullptr;
   float *attrs_ = nullptr, *conf_ = nullptr, *kernel_ms_ = nullptr;
-  unsigned long long* gsum_ = nullptr;
-  uint32_t* gcnt_ = nullptr;
-  uint32_t *hist_ = nullptr, *status_ = nullptr, *confusion_ = nullptr;
-  unsigned long long *misc_ = nullptr, *dbg_ = nullptr;
-  double *stats_ = nullptr, *stats_count_ = nullptr;
-  // results block views (device)
-  double *post_ = nullptr, *gconf_ = nullptr;
-  float* feat_ = nullptr;
-  int32_t* pred_ = nullptr;
-  uint32_t* evbits_ = nullptr;
-  // events
-  std::vector<hipEvent_t> h2d_done_, h2d_part_, head_done_, compute_done_, comm_done_;
-  std::vector<hipEvent_t> t_start_, t_copy_end_, t_comp0_, t_comp1_, t_end_;
   std::map<std::tuple<int, int, bool, bool>, hipGraphExec_t> graphs_;
   std::vector<bool> warm_;
   std::vector<hipGraph_t> graph_defs_;

@@ -2,6 +2,7 @@
 #include "engine.h"
 #include "mislo_packet_kernels.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cmath>
@@ -76,30 +77,85 @@ void to_host(const void* src, void* dst, size_t bytes, hipStream_t st) {
                      static_cast<uint4*>(dst), n16);
 }
 
-// pinned, device-visible host memory the kernels store into (uncached on the device side)
-void* host_block(size_t bytes) {
-  void* h = nullptr;
-  HIPCHECK(hipHostMalloc(&h, (bytes + 15) & ~size_t(15), hipHostMallocCoherent | hipHostMallocMapped));
-  std::memset(h, 0, bytes);
-  return h;
+constexpr unsigned kEvWait = hipEventDisableTiming | hipEventBlockingSync;  // events the host sleeps on
+
+// an integer environment knob, `unset` where it is not set
+int env_int(const char* name, int unset) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : unset;
 }
 
-template <class T>
-T* dalloc(size_t n) {
-  void* p = nullptr;
-  HIPCHECK(hipMalloc(&p, n * sizeof(T) + 64));
-  return static_cast<T*>(p);
-}
-
-hipEvent_t mk_event(bool timing) {
-  hipEvent_t e;
-  HIPCHECK(hipEventCreateWithFlags(&e, timing ? hipEventDefault : (hipEventDisableTiming | hipEventBlockingSync)));
-  return e;
-}
+// laps of a steady clock, each added to an accumulator in microseconds
+struct Lap {
+  using clock = std::chrono::steady_clock;
+  clock::time_point t = clock::now();
+  void operator()(double& acc) {
+    const auto n = clock::now();
+    acc += std::chrono::duration<double, std::micro>(n - t).count();
+    t = n;
+  }
+};
 
 }  // namespace
 
 void engine_set_tables(const Tables& t) { set_tables(&t); }
+
+// What the engine creates is recorded in own_, which destroys it: events, memory, streams.
+template <class T>
+T* WindowEngine::dalloc(size_t n, bool zero) {
+  void* p = nullptr;
+  HIPCHECK(hipMalloc(&p, n * sizeof(T) + 64));
+  own_.dev.push_back(p);
+  if (zero) HIPCHECK(hipMemset(p, 0, n * sizeof(T)));
+  return static_cast<T*>(p);
+}
+
+void* WindowEngine::host_alloc(size_t bytes, unsigned flags) {
+  void* h = nullptr;
+  HIPCHECK(hipHostMalloc(&h, bytes, flags));
+  own_.host.push_back(h);
+  return h;
+}
+
+// pinned, device-visible host memory the kernels store into (uncached on the device side)
+void* WindowEngine::host_block(size_t bytes) {
+  void* h = host_alloc((bytes + 15) & ~size_t(15), hipHostMallocCoherent | hipHostMallocMapped);
+  std::memset(h, 0, bytes);
+  return h;
+}
+
+hipEvent_t WindowEngine::mk_event(unsigned flags) {
+  hipEvent_t e;
+  HIPCHECK(hipEventCreateWithFlags(&e, flags));
+  own_.events.push_back(e);
+  return e;
+}
+
+hipStream_t WindowEngine::mk_stream(bool high_priority) {
+  hipStream_t s;
+  int lo = 0, hi = 0;
+  if (high_priority) {
+    HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIPCHECK(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, hi));
+  } else {
+    HIPCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  }
+  own_.streams.push_back(s);
+  return s;
+}
+
+void WindowEngine::Owner::free_dev(void* p) {
+  if (!p) return;
+  dev.erase(std::find(dev.begin(), dev.end(), p));
+  HIPCHECK(hipFree(p));
+}
+
+WindowEngine::Owner::~Owner() {
+  for (hipEvent_t e : events) (void)hipEventDestroy(e);
+  for (void* p : host) (void)hipHostFree(p);
+  for (void* p : dev) (void)hipFree(p);
+  for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+}
 
 WindowEngine::WindowEngine(const EngineConfig& cfg) : cfg_(cfg) {
   if (cfg.sig_cap <= 0 || cfg.span_cap <= 0 || cfg.group_cap <= 0 || cfg.group_cap > 4096)
@@ -147,31 +203,19 @@ void WindowEngine::alloc() {
   // hardware queue (the agent's GPU_MAX_HW_QUEUES=1) the two streams' commands run in order on
   // that queue anyway, and the copy stream's first use maps another ~173 MB queue save area
   // (tools/rss_probe.py); the bench keeps the two streams (copy / compute overlap on 4 queues).
-  const bool one_stream = [] {
-    const char* v = getenv("MISLO_ONE_STREAM");
-    return v && atoi(v) == 1;
-  }();
-  HIPCHECK(hipStreamCreateWithFlags(&compute_, hipStreamNonBlocking));
-  if (one_stream) copy_ = compute_;
-  else HIPCHECK(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking));
-  {  // MISLO_SPIN_WAIT=1: wait() polls its event instead of sleeping on it
-    const char* v = getenv("MISLO_SPIN_WAIT");
-    spin_ = v && atoi(v) == 1;
-  }
-  {  // MISLO_COPY_STREAMS=2 splits a window's DMA over two streams (measured slower: the
-     // second stream's large copy blocks the issuing thread ~0.2 ms per window)
-    const char* v = getenv("MISLO_COPY_STREAMS");
-    if (v && atoi(v) == 2 && !one_stream) HIPCHECK(hipStreamCreateWithFlags(&copy2_, hipStreamNonBlocking));
-    else copy2_ = copy_;
-  }
-  {
-    // Window overlap (engine.h): the front stage on a stream of its own. Not for an engine sized
-    // for the exchange (its windows run the two-part serial chain), and switched off by init_comm.
-    const char* v = getenv("MISLO_WINDOW_OVERLAP");
-    overlap_ = (v ? atoi(v) == 1 : !one_stream) && !one_stream && !(cfg_.xchg_cap > 0 && cfg_.import_cap > 0);
-    if (overlap_) HIPCHECK(hipStreamCreateWithFlags(&front_, hipStreamNonBlocking));
-    slots_ = gens_ + (overlap_ ? 1 : 0);
-  }
+  const bool one_stream = env_int("MISLO_ONE_STREAM", 0) == 1;
+  compute_ = mk_stream();
+  copy_ = one_stream ? compute_ : mk_stream();
+  spin_ = env_int("MISLO_SPIN_WAIT", 0) == 1;  // wait() polls its event instead of sleeping on it
+  // MISLO_COPY_STREAMS=2 splits a window's DMA over two streams (measured slower: the second
+  // stream's large copy blocks the issuing thread ~0.2 ms per window)
+  copy2_ = env_int("MISLO_COPY_STREAMS", 0) == 2 && !one_stream ? mk_stream() : copy_;
+  // Window overlap (engine.h): the front stage on a stream of its own. Not for an engine sized
+  // for the exchange (its windows run the two-part serial chain), and switched off by init_comm.
+  overlap_ = env_int("MISLO_WINDOW_OVERLAP", !one_stream) == 1 && !one_stream &&
+             !(cfg_.xchg_cap > 0 && cfg_.import_cap > 0);
+  if (overlap_) front_ = mk_stream();
+  slots_ = gens_ + (overlap_ ? 1 : 0);
   {
     // The span side of the chain (decode, partition, sort, the probe's work list) on a second
     // stream, overlapping the signal side's decode: on by default in the serial chain where the
@@ -184,8 +228,7 @@ void WindowEngine::alloc() {
     // copy, front, compute, side and those no longer fit the four hardware queues one each --
     // streams that share a queue wait for each other's copies and event waits. Measured 0.60
     // with the branch against 0.48 ms per window without (profiles/window_overlap/README.md).
-    const char* v = getenv("MISLO_SPAN_STREAM");
-    if (v ? atoi(v) == 1 : (!one_stream && !overlap_)) enable_span_branch();
+    if (env_int("MISLO_SPAN_STREAM", !one_stream && !overlap_) == 1) enable_span_branch();
   }
   // one GPU: the window's tail (packet accumulate, timing) runs on the compute stream; a comm
   // stream of its own exists only with a communicator (init_comm). Every stream backs a
@@ -198,61 +241,37 @@ void WindowEngine::alloc() {
   off_user_ = (off_kern_ + kern_bytes() + 63) & ~size_t(63);
   off_span_ = off_user_ + 64 * (size_t)cfg_.user_cap;
   in_bytes_ = off_span_ + 64 * (size_t)S;
-  for (int b = 0; b < nb_; ++b) {
-    in_dev_.push_back(dalloc<uint8_t>(in_bytes_));
-    HIPCHECK(hipMemset(in_dev_.back(), 0, in_bytes_));
-    void* h = nullptr;
-    head_host_.push_back(static_cast<uint8_t*>(host_block(head)));
-    staging_.push_back(nullptr);  // pinned staging is allocated on first use (unregistered rings only)
-    packet_dev_.push_back(dalloc<double>(kPacketLen));
-    HIPCHECK(hipMemset(packet_dev_.back(), 0, kPacketLen * sizeof(double)));
-    packet_host_.push_back(static_cast<double*>(host_block(kPacketLen * sizeof(double))));
-    h2d_done_.push_back(mk_event(false));
-    h2d_part_.push_back(mk_event(false));
-    head_done_.push_back(mk_event(false));
-    compute_done_.push_back(mk_event(false));
-    comm_done_.push_back(mk_event(false));
-    front_done_.push_back(mk_event(false));
-    t_start_.push_back(mk_event(true));
-    t_copy_end_.push_back(mk_event(true));
-    t_comp0_.push_back(mk_event(true));
-    t_comp1_.push_back(mk_event(true));
-    t_end_.push_back(mk_event(true));
+  // per buffer: the comm stream gathers window k's results while window k + 1 computes
+  const ResultLayout lay = layout();
+  bufs_.assign(nb_, Buf{});
+  for (Buf& buf : bufs_) {
+    buf.in = dalloc<uint8_t>(in_bytes_, true);
+    buf.head_host = static_cast<uint8_t*>(host_block(head));
+    buf.packet_dev = dalloc<double>(kPacketLen, true);
+    buf.packet_host = static_cast<double*>(host_block(kPacketLen * sizeof(double)));
+    for (hipEvent_t* e : {&buf.h2d_done, &buf.h2d_part, &buf.head_done, &buf.compute_done, &buf.comm_done,
+                          &buf.front_done, &buf.xchg_done})
+      *e = mk_event(kEvWait);
+    for (hipEvent_t* e : {&buf.t_start, &buf.t_copy_end, &buf.t_comp0, &buf.t_comp1, &buf.t_end})
+      *e = mk_event(hipEventDefault);  // timing
+    buf.res_host = static_cast<uint8_t*>(host_block(lay.bytes()));
+    buf.res_dev = dalloc<uint8_t>(lay.bytes(), true);
+    buf.res = lay.view(buf.res_dev);
+    buf.imp = cfg_.import_cap ? dalloc<SigRec>(cfg_.import_cap) : nullptr;
   }
-  warm_.assign(8 * nb_, false);
-  // per-incident results block: [post G*16 f64][gconf G f64][feat G*16 f32][pred G i32][evbits G*16 u32]
-  // [sli G*2 u32][app G*2 u32][late G*2 u32]
-  const size_t o_gconf = 16 * G * 8, o_feat = o_gconf + G * 8, o_pred = o_feat + 16 * G * 4, o_ev = o_pred + G * 4;
-  const size_t o_sli = o_ev + 16 * G * 4;
-  res_bytes_ = o_sli + 6 * G * 4;
-  for (int b = 0; b < nb_; ++b) {
-    res_host_.push_back(static_cast<uint8_t*>(host_block(res_bytes_)));
-  }
-  for (int b = 0; b < nb_; ++b) {  // per buffer: the comm stream gathers window k's while k+1 computes
-    res_dev_.push_back(dalloc<uint8_t>(res_bytes_));
-    HIPCHECK(hipMemset(res_dev_.back(), 0, res_bytes_));
-  }
+  warm_.assign(kStageSlots * nb_, false);
   // pod metadata, ring accounting, the trace id -> hash table
-  pod_sn_ = dalloc<uint32_t>(kPodRows);
-  HIPCHECK(hipMemset(pod_sn_, 0, kPodRows * 4));
-  {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, kPodRows * 4, hipHostMallocDefault));
-    std::memset(h, 0, kPodRows * 4);
-    pod_host_ = static_cast<uint32_t*>(h);
-  }
-  trace_hash_ = dalloc<unsigned long long>(kTraceIdRows);
-  HIPCHECK(hipMemset(trace_hash_, 0, (size_t)kTraceIdRows * 8));
+  pod_sn_ = dalloc<uint32_t>(kPodRows, true);
+  pod_host_ = static_cast<uint32_t*>(host_alloc(kPodRows * 4, hipHostMallocDefault));
+  std::memset(pod_host_, 0, kPodRows * 4);
+  trace_hash_ = dalloc<unsigned long long>(kTraceIdRows, true);
   // other GPUs' trace rows and the selection of this GPU's; the generations' state
-  tmax_ = dalloc<unsigned long long>(1);
-  HIPCHECK(hipMemset(tmax_, 0, 8));
-  remote_n_ = dalloc<uint32_t>(nb_);
-  HIPCHECK(hipMemset(remote_n_, 0, nb_ * 4));
+  tmax_ = dalloc<unsigned long long>(1, true);
+  remote_n_ = dalloc<uint32_t>(nb_, true);
   // the state both stages of a window touch: per buffer with overlapped windows, else one set
   for (int i = 0; i < (overlap_ ? nb_ : 1); ++i) {
     BufSet s{};
-    s.rows = dalloc<int>(16);
-    HIPCHECK(hipMemset(s.rows, 0, 16 * sizeof(int)));
+    s.rows = dalloc<int>(16, true);
     s.ring_state = dalloc<uint32_t>(kRsLen);
     s.gen = dalloc<GenMeta>(1);
     GenMeta g{};
@@ -264,8 +283,7 @@ void WindowEngine::alloc() {
     s.s_items = dalloc<uint32_t>(kKeyTypes * S);
     s.s_pre = dalloc<PreSpan>((size_t)kKeyTypes * S);
     s.s_rec = dalloc<SpanRec>(S);
-    s.probe_work = dalloc<uint32_t>(kProbeWorkLen);
-    HIPCHECK(hipMemset(s.probe_work, 0, kProbeWorkLen * 4));
+    s.probe_work = dalloc<uint32_t>(kProbeWorkLen, true);
     s.top3 = dalloc<unsigned long long>(3 * S);
     s.cnt = dalloc<uint32_t>(S);
     s.gsum = dalloc<unsigned long long>((size_t)kGroupStripes * G * kSlots);
@@ -279,45 +297,37 @@ void WindowEngine::alloc() {
     s.stats_count = dalloc<double>(kMaxDomains);
     sets_.push_back(s);
   }
-  set_buffer(0);
+  for (int b = 0; b < nb_; ++b) {  // sets_ is complete: its elements no longer move
+    bufs_[b].b = b;
+    bufs_[b].set = &sets_[overlap_ ? b : 0];
+    bufs_[b].gen_prev = sets_[overlap_ ? (b + nb_ - 1) % nb_ : 0].gen;
+    bufs_[b].remote_n = remote_n_ + b;
+  }
   sel_cnt_ = dalloc<uint32_t>(1024);
   sel_off_ = dalloc<uint32_t>(1024);
-  for (int b = 0; b < nb_; ++b) imp_.push_back(cfg_.import_cap ? dalloc<SigRec>(cfg_.import_cap) : nullptr);
   xstride_ = sizeof(XRec) * (1 + (size_t)cfg_.xchg_cap);  // [24-byte header: row count | XRec rows]
   if (cfg_.xchg_cap) {
-    xsend_ = dalloc<uint8_t>(xstride_);
-    HIPCHECK(hipMemset(xsend_, 0, xstride_));
-    const char* tp = getenv("MISLO_SEL_TWO_PASS");
-    if (!(tp && atoi(tp) == 1)) {  // the fused selection's ballot masks (segment 0's decode geometry)
+    xsend_ = dalloc<uint8_t>(xstride_, true);
+    if (env_int("MISLO_SEL_TWO_PASS", 0) != 1) {  // the fused selection's ballot masks (segment 0's decode geometry)
       sel_stride_ = decode_sel_stride(n_rows_);
       sel_mask_ = dalloc<unsigned long long>((size_t)decode_grid(n_rows_) * (size_t)sel_stride_);
     }
   }
   // context table: every id the kernel or the host encoder can assign, HBM-resident
-  ctx_tab_ = dalloc<uint32_t>((size_t)kCtxRows * 4);
-  HIPCHECK(hipMemset(ctx_tab_, 0, (size_t)kCtxRows * 16));
-  totals_ = dalloc<double>(kPacketLen);
-  HIPCHECK(hipMemset(totals_, 0, kPacketLen * sizeof(double)));
-  stats_acc_ = dalloc<double>(kStatsLen);
-  HIPCHECK(hipMemset(stats_acc_, 0, kStatsLen * sizeof(double)));
-  p0_ = dalloc<double>(2 * kSlots * 16);  // the Beta prior's table, then the likelihood floor
-  HIPCHECK(hipMemset(p0_, 0, 2 * kSlots * 16 * sizeof(double)));
-  model_dev_ = dalloc<uint8_t>(sizeof(PosteriorModel));
-  HIPCHECK(hipMemset(model_dev_, 0, sizeof(PosteriorModel)));
-  app_dev_ = dalloc<AppModel>(1);
-  HIPCHECK(hipMemset(app_dev_, 0, sizeof(AppModel)));  // on = 0: no application evidence until set
-  for (int i = 0; i < max_ahead_ + 2; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, sizeof(PosteriorModel), hipHostMallocDefault));
-    model_host_.push_back(static_cast<uint8_t*>(h));
-  }
+  ctx_tab_ = dalloc<uint32_t>((size_t)kCtxRows * 4, true);
+  totals_ = dalloc<double>(kPacketLen, true);
+  stats_acc_ = dalloc<double>(kStatsLen, true);
+  p0_ = dalloc<double>(2 * kSlots * 16, true);  // the Beta prior's table, then the likelihood floor
+  model_dev_ = dalloc<uint8_t>(sizeof(PosteriorModel), true);
+  app_dev_ = dalloc<AppModel>(1, true);  // on = 0: no application evidence until set
+  for (int i = 0; i < max_ahead_ + 2; ++i)
+    model_host_.push_back(static_cast<uint8_t*>(host_alloc(sizeof(PosteriorModel), hipHostMallocDefault)));
   g_status_ = dalloc<uint8_t>(N);
   g_part_ = dalloc<PartCodes>(N);
   // other GPUs' rows decode in blocks of their own (<= 7 peers' exchange blocks)
   nblk_imp_ = cfg_.xchg_cap ? decode_grid(7 * cfg_.xchg_cap) : 0;
   g_part_blk_ = dalloc<uint32_t>((size_t)(nblk_sig_ + nblk_imp_) * kKeyTypes * kParts);
   g_part_off_ = dalloc<uint32_t>((size_t)(nblk_sig_ + nblk_imp_) * kKeyTypes * kParts);
-  for (int b = 0; b < nb_; ++b) xchg_done_.push_back(mk_event(false));
   g_part_tot_ = dalloc<uint32_t>(kKeyTypes * kParts);
   // resident generations: rows, partition lists, list keys and offsets of the last gens_ windows,
   // over slots_ physical slots (one spare with overlapped windows: the next window's front stage
@@ -338,73 +348,27 @@ void WindowEngine::alloc() {
 }
 
 WindowEngine::~WindowEngine() {
-  hipDeviceSynchronize();
-  for (auto& kv : graphs_) hipGraphExecDestroy(kv.second);
-  for (auto g : graph_defs_) hipGraphDestroy(g);
+  (void)hipDeviceSynchronize();
+  for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
+  for (auto g : graph_defs_) (void)hipGraphDestroy(g);
   if (xcomm_) ncclCommDestroy(xcomm_);
   if (comm_) ncclCommDestroy(comm_);
-  auto evs = {&t_copy_end_, &h2d_done_, &h2d_part_, &head_done_, &compute_done_, &comm_done_, &t_start_, &t_comp0_, &t_comp1_, &t_end_};
-  for (auto* v : evs)
-    for (auto e : *v) hipEventDestroy(e);
-  for (auto& r : registered_) hipHostUnregister(const_cast<uint8_t*>(r.first));
-  for (auto p : head_host_) hipHostFree(p);
-  for (auto p : staging_)
-    if (p) hipHostFree(p);
-  if (pod_host_) hipHostFree(pod_host_);
-  for (auto p : res_all_host_) hipHostFree(p);
-  for (auto p : res_all_dev_) hipFree(p);
-  for (auto p : imp_)
-    if (p) hipFree(p);
-  for (auto e : xchg_done_) hipEventDestroy(e);
-  for (auto p : packet_host_) hipHostFree(p);
-  for (auto p : res_host_) hipHostFree(p);
-  for (auto p : model_host_) hipHostFree(p);
-  for (auto p : in_dev_) hipFree(p);
-  for (auto p : packet_dev_) hipFree(p);
-  for (auto p : res_dev_) hipFree(p);
-  for (auto e : front_done_) hipEventDestroy(e);
-  for (const BufSet& s : sets_) {
-    void* per[] = {s.gen, s.rows, s.ring_state, s.hist, s.status, s.confusion, s.cnt, s.gcnt, s.misc, s.dbg, s.top3,
-                   s.gsum, s.stats, s.stats_count, s.s_rec, s.s_part, s.s_items, s.s_part_base, s.probe_work, s.s_pre};
-    for (void* p : per)
-      if (p) hipFree(p);
-  }
-  void* bufs[] = {ctx_tab_, totals_, stats_acc_, p0_, model_dev_, g_status_, g_part_, g_part_blk_, g_part_off_,
-                  g_part_tot_, g_part_base_, g_items_, g_rec_, s_part_blk_, s_part_off_, s_part_tot_,
-                  attrs_, conf_, kernel_ms_, pod_sn_, trace_hash_,
-                  tmax_, remote_n_, sel_cnt_, sel_off_, sel_mask_, xsend_, xrecv_, g_keys_, app_dev_};
-  for (void* p : bufs)
-    if (p) hipFree(p);
-  if (copy_ && copy_ != compute_) hipStreamDestroy(copy_);
-  if (copy2_ && copy2_ != copy_) hipStreamDestroy(copy2_);
-  if (compute_) hipStreamDestroy(compute_);
-  if (side_) hipStreamDestroy(side_);
-  if (front_) hipStreamDestroy(front_);
-  for (hipEvent_t e : {ev_fork_, ev_sigbase_, ev_spans_})
-    if (e) hipEventDestroy(e);
-  if (comm_stream_ && comm_stream_ != compute_) hipStreamDestroy(comm_stream_);
-}
+  for (auto& r : registered_) (void)hipHostUnregister(const_cast<uint8_t*>(r.first));
+}  // then own_: events, memory, streams
 
 void WindowEngine::enable_span_branch() {
   if (branch_) return;
-  int lo = 0, hi = 0;
-  HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  const char* pv = getenv("MISLO_SPAN_STREAM_PRIO");  // 1 = the highest priority
-  if (pv && atoi(pv) == 1)
-    HIPCHECK(hipStreamCreateWithPriority(&side_, hipStreamNonBlocking, hi));
-  else
-    HIPCHECK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-  for (hipEvent_t* e : {&ev_fork_, &ev_sigbase_, &ev_spans_})
-    HIPCHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  const char* xv = getenv("MISLO_XCHG_SPAN_SIDE");  // 0: the exchange path's span side in part 2
-  xspan_ = !(xv && atoi(xv) == 0);
+  side_ = mk_stream(env_int("MISLO_SPAN_STREAM_PRIO", 0) == 1);  // 1 = the highest priority
+  for (hipEvent_t* e : {&ev_fork_, &ev_sigbase_, &ev_spans_}) *e = mk_event(hipEventDisableTiming);
+  xspan_ = env_int("MISLO_XCHG_SPAN_SIDE", 1) != 0;  // 0: the exchange path's span side in part 2
   branch_ = true;
 }
 
-SignalCols WindowEngine::sig_cols() const {
-  return SignalCols{g_rec_, g_status_, g_part_, g_items_, g_keys_, g_part_base_, gen_, (int64_t)n_rows_, gens_, slots_};
+SignalCols WindowEngine::sig_cols(const Buf& buf) const {
+  return SignalCols{g_rec_, g_status_, g_part_, g_items_, g_keys_, g_part_base_, buf.set->gen, (int64_t)n_rows_, gens_,
+                    slots_};
 }
-SpanCols WindowEngine::span_cols() const { return SpanCols{s_rec_, s_part_}; }
+SpanCols WindowEngine::span_cols(const Buf& buf) const { return SpanCols{buf.set->s_rec, buf.set->s_part}; }
 
 bool WindowEngine::register_host(const void* ptr, size_t bytes) {
   if (!ptr || !bytes) return false;
@@ -434,11 +398,7 @@ size_t WindowEngine::dma(const std::vector<Seg>& segs, uint8_t* dst, size_t cap,
     if (off + s.bytes > cap) throw std::invalid_argument("window input exceeds the engine's capacity");
     const void* src = s.ptr;
     if (!registered(s.ptr, s.bytes)) {
-      if (!staging) {
-        void* h = nullptr;
-        HIPCHECK(hipHostMalloc(&h, in_bytes_ - off_kern_, hipHostMallocDefault));
-        staging = static_cast<uint8_t*>(h);
-      }
+      if (!staging) staging = static_cast<uint8_t*>(host_alloc(in_bytes_ - off_kern_, hipHostMallocDefault));
       std::memcpy(staging + st_off, s.ptr, s.bytes);
       src = staging + st_off;
       st_off += s.bytes;
@@ -453,7 +413,7 @@ size_t WindowEngine::dma(const std::vector<Seg>& segs, uint8_t* dst, size_t cap,
 }
 
 bool WindowEngine::h2d_done(int64_t k) {
-  for (hipEvent_t ev : {h2d_done_[k % nb_], h2d_part_[k % nb_]}) {  // both copy streams
+  for (hipEvent_t ev : {bufs_[k % nb_].h2d_done, bufs_[k % nb_].h2d_part}) {  // both copy streams
     const hipError_t e = hipEventQuery(ev);
     if (e == hipErrorNotReady) return false;
     HIPCHECK(e);
@@ -462,219 +422,181 @@ bool WindowEngine::h2d_done(int64_t k) {
 }
 
 void WindowEngine::wait_h2d(int64_t k) {
-  HIPCHECK(hipEventSynchronize(h2d_done_[k % nb_]));
-  HIPCHECK(hipEventSynchronize(h2d_part_[k % nb_]));
-}
-
-// This buffer's per-incident result pointers and its set of the state both stages of a window
-// touch (read by the kernels the parts launch; every run_* starts here).
-void WindowEngine::set_buffer(int b) {
-  const int G = cfg_.group_cap;
-  const BufSet& s = sets_[set_of(b)];
-  gen_ = s.gen;
-  gen_prev_ = sets_[set_of((b + nb_ - 1) % nb_)].gen;  // the previous window's buffer
-  rows_ = s.rows;
-  ring_state_ = s.ring_state;
-  hist_ = s.hist, status_ = s.status, confusion_ = s.confusion, cnt_ = s.cnt, gcnt_ = s.gcnt;
-  misc_ = s.misc, dbg_ = s.dbg, top3_ = s.top3, gsum_ = s.gsum;
-  stats_ = s.stats, stats_count_ = s.stats_count;
-  s_rec_ = s.s_rec, s_part_ = s.s_part, s_items_ = s.s_items, s_part_base_ = s.s_part_base;
-  probe_work_ = s.probe_work, s_pre_ = s.s_pre;
-  uint8_t* r = res_dev_[b];  // this buffer's per-incident results block
-  const size_t o_gconf = 16 * (size_t)G * 8, o_feat = o_gconf + (size_t)G * 8, o_pred = o_feat + 16 * (size_t)G * 4;
-  const size_t o_ev = o_pred + (size_t)G * 4, o_sli = o_ev + 16 * (size_t)G * 4;
-  post_ = reinterpret_cast<double*>(r);
-  gconf_ = reinterpret_cast<double*>(r + o_gconf);
-  feat_ = reinterpret_cast<float*>(r + o_feat);
-  pred_ = reinterpret_cast<int32_t*>(r + o_pred);
-  evbits_ = reinterpret_cast<uint32_t*>(r + o_ev);
-  sli_ = reinterpret_cast<uint32_t*>(r + o_sli);
-  app_ = sli_ + 2 * (size_t)G;
-  late_ = sli_ + 4 * (size_t)G;
+  HIPCHECK(hipEventSynchronize(bufs_[k % nb_].h2d_done));
+  HIPCHECK(hipEventSynchronize(bufs_[k % nb_].h2d_part));
 }
 
 // The head of a window: the accumulators reset, the next generation slot, the window's rows.
-void WindowEngine::run_begin(int b, hipStream_t st) {
-  set_buffer(b);
-  const int* counts = reinterpret_cast<const int*>(in_dev_[b]);
+void WindowEngine::run_begin(const Buf& buf, hipStream_t st) {
+  const BufSet& s = *buf.set;
   const int S = cfg_.span_cap, G = cfg_.group_cap;
   FillList fl{};
   auto add = [&](void* p, size_t bytes, uint32_t v) { fl.seg[fl.count++] = FillSeg{(uint32_t*)p, (uint32_t)(bytes / 4), v}; };
-  add(hist_, kSlots * kBuckets * 4, 0);
-  add(status_, kSlots * 3 * 4, 0);
-  add(misc_, kPacketMisc * 8, 0);
-  add(dbg_, kPacketDbg * 8, 0);
-  add(confusion_, kMaxDomains * kMaxDomains * 4, 0);
-  add(stats_, 32 * 32 * 8, 0);
-  add(stats_count_, kMaxDomains * 8, 0);
-  add(top3_, 3 * (size_t)S * 8, 0xFFFFFFFFu);
-  add(cnt_, (size_t)S * 4, 0);
-  add(gsum_, (size_t)kGroupStripes * G * kSlots * 8, 0);
-  add(gcnt_, (size_t)kGroupStripes * G * kSlots * 4, 0);
-  add(sli_, (size_t)G * 6 * 4, 0);  // + the application retrieval counts (app_) and late breaches (late_)
+  add(s.hist, kSlots * kBuckets * 4, 0);
+  add(s.status, kSlots * 3 * 4, 0);
+  add(s.misc, kPacketMisc * 8, 0);
+  add(s.dbg, kPacketDbg * 8, 0);
+  add(s.confusion, kMaxDomains * kMaxDomains * 4, 0);
+  add(s.stats, 32 * 32 * 8, 0);
+  add(s.stats_count, kMaxDomains * 8, 0);
+  add(s.top3, 3 * (size_t)S * 8, 0xFFFFFFFFu);
+  add(s.cnt, (size_t)S * 4, 0);
+  add(s.gsum, (size_t)kGroupStripes * G * kSlots * 8, 0);
+  add(s.gcnt, (size_t)kGroupStripes * G * kSlots * 4, 0);
+  add(buf.res.sli, (size_t)G * 6 * 4, 0);  // + the application retrieval counts (app) and late breaches (late)
   // + the next generation slot and the halo cut-offs (the finished window's tmax is read before
   // its reset), the ring state, no other GPUs' rows until merged, the window's rows
-  launch_window_begin(fl, gen_, gen_prev_, tmax_, gens_, slots_, (long long)llround(cfg_.halo_ms * 1e6), ring_state_,
-                      remote_n_ + b, counts, n_rows_, rows_, st);
+  launch_window_begin(fl, s.gen, buf.gen_prev, tmax_, gens_, slots_, (long long)llround(cfg_.halo_ms * 1e6),
+                      s.ring_state, buf.remote_n, buf.counts(), n_rows_, s.rows, st);
 }
 
-// The captured part of a window: everything between the DMA and the packet.
 // Part 1 of a window: accumulators, definitions, the decode of the window's records and the
 // halo it imported; with the GPU exchange, this window's trace-tagged rows for the others.
-void WindowEngine::run_part1(int b, hipStream_t st, bool xchg) {
-  uint8_t* in = in_dev_[b];
-  const int* counts = reinterpret_cast<const int*>(in);
+void WindowEngine::run_part1(const Buf& buf, hipStream_t st, bool xchg) {
+  const BufSet& s = *buf.set;
+  const int* counts = buf.counts();
   const int N = n_rows_;
-  if (!(xchg && xspan_)) run_begin(b, st);  // else its own launch (submit: part 4)
-  else set_buffer(b);
+  if (!(xchg && xspan_)) run_begin(buf, st);  // else its own launch (submit: Stage::XchgHead)
   // the span branch in the one-GPU chain: forked inside the window's graph and joined before the
   // probe. With the exchange, forked inside part 1's graph and joined before the exchange it
   // measured 0.76 against 0.62 ms per window (bench.py --rccl-self); there the span side is a
-  // graph of its own on side_ instead (xspan_, submit: parts 4 and 3)
-  if (branch_ && !xchg) run_span_branch(b, st);
+  // graph of its own on side_ instead (xspan_, submit: Stage::XchgHead and Stage::XchgSpans)
+  if (branch_ && !xchg) run_span_branch(buf, st);
   const TraceIds tt{trace_hash_, kTraceIdRows};
-  launch_ring_defs(in + off_kern_, counts, cfg_.sig_cap, ctx_tab_, kCtxRows, pod_sn_, kPodRows, tt, ring_state_, st);
+  launch_ring_defs(buf.in + off_kern_, counts, cfg_.sig_cap, ctx_tab_, kCtxRows, pod_sn_, kPodRows, tt, s.ring_state,
+                   st);
   const bool fused_sel = xchg && sel_mask_;  // the selection's count and masks left by the decode
-  launch_decode_window(in + off_kern_, in + off_user_, counts, rows_, N, imp_[b], ctx_tab_, (int)kCtxRows, tt,
-                       ring_state_, tmax_, pod_sn_, kPodRows, sig_cols(), hist_, status_, g_part_blk_, misc_, st, 0, 0, 0,
-                       rec_shard_rank(), rec_shard_world(), fused_sel ? sel_cnt_ : nullptr,
+  launch_decode_window(buf.in + off_kern_, buf.in + off_user_, counts, s.rows, N, buf.imp, ctx_tab_, (int)kCtxRows, tt,
+                       s.ring_state, tmax_, pod_sn_, kPodRows, sig_cols(buf), s.hist, s.status, g_part_blk_, s.misc, st,
+                       0, 0, 0, rec_shard_rank(), rec_shard_world(), fused_sel ? sel_cnt_ : nullptr,
                        fused_sel ? sel_mask_ : nullptr, sel_stride_);
   // this window's warn-level trace-tagged rows, as the other GPUs will import them
   if (fused_sel)
-    launch_select_masked(sig_cols(), rows_, N, sel_cnt_, sel_off_, sel_mask_, sel_stride_,
+    launch_select_masked(sig_cols(buf), s.rows, N, sel_cnt_, sel_off_, sel_mask_, sel_stride_,
                          reinterpret_cast<XRec*>(xsend_ + sizeof(XRec)), reinterpret_cast<uint32_t*>(xsend_),
-                         (uint32_t)cfg_.xchg_cap, st, dbg_ + kDbgXchgDropped);
+                         (uint32_t)cfg_.xchg_cap, st, s.dbg + kDbgXchgDropped);
   else if (xchg)
-    launch_select(sig_cols(), rows_, counts, N, sel_cnt_, sel_off_, reinterpret_cast<XRec*>(xsend_ + sizeof(XRec)),
-                  reinterpret_cast<uint32_t*>(xsend_), (uint32_t)cfg_.xchg_cap, st, dbg_ + kDbgXchgDropped);
+    launch_select(sig_cols(buf), s.rows, counts, N, sel_cnt_, sel_off_, reinterpret_cast<XRec*>(xsend_ + sizeof(XRec)),
+                  reinterpret_cast<uint32_t*>(xsend_), (uint32_t)cfg_.xchg_cap, st, s.dbg + kDbgXchgDropped);
 }
 
-// Part 2: [the other GPUs' rows] -> partition -> spans -> join (this window's spans x every
-// generation's visible rows) -> posterior -> packet.
-void WindowEngine::run_part2(int b, int n_groups, bool with_labels, bool learn, hipStream_t st, bool xchg) {
-  run_join_front(b, st, xchg);
-  run_join_back(b, n_groups, with_labels, learn, st);
-}
-
-void WindowEngine::run_join_front(int b, hipStream_t st, bool xchg) {
-  set_buffer(b);
-  uint8_t* in = in_dev_[b];
-  const int* counts = reinterpret_cast<const int*>(in);
+// Part 2, first half: [the other GPUs' rows] -> partition -> spans (unless they ran beside part 1).
+void WindowEngine::run_join_front(const Buf& buf, hipStream_t st, bool xchg) {
+  const BufSet& s = *buf.set;
   const int N = n_rows_;
   if (xchg) {
     const TraceIds tt{trace_hash_, kTraceIdRows};
-    launch_decode_window(in + off_kern_, in + off_user_, counts, rows_, N, imp_[b], ctx_tab_, (int)kCtxRows, tt,
-                         ring_state_, tmax_, pod_sn_, kPodRows, sig_cols(), hist_, status_, g_part_blk_, misc_, st,
-                         1, nblk_imp_, nblk_sig_, rec_shard_rank(), rec_shard_world());
+    launch_decode_window(buf.in + off_kern_, buf.in + off_user_, buf.counts(), s.rows, N, buf.imp, ctx_tab_,
+                         (int)kCtxRows, tt, s.ring_state, tmax_, pod_sn_, kPodRows, sig_cols(buf), s.hist, s.status,
+                         g_part_blk_, s.misc, st, 1, nblk_imp_, nblk_sig_, rec_shard_rank(), rec_shard_world());
   }
   const bool branched = branch_ && !xchg;
   // with the span branch: the signal bases are what the branch's probe work list waits for
   hipEvent_t sig_base = branched ? ev_sigbase_ : nullptr;
   // without the span branch: the span side first, so the signal scatter's launch can build the
   // probe's work list next to it (it needs both sides' list offsets); with the exchange and
-  // xspan_ the span side ran on side_ next to part 1 (submit: part 3)
-  if (!branched && !(xchg && xspan_)) run_spans(b, st);
-  const uint32_t* wspan = branched ? nullptr : s_part_base_;
+  // xspan_ the span side ran on side_ next to part 1 (submit: Stage::XchgSpans)
+  if (!branched && !(xchg && xspan_)) run_spans(buf, st);
+  const uint32_t* wspan = branched ? nullptr : s.s_part_base;
   const JoinParams* wjp = branched ? nullptr : &jp_;
-  uint32_t* wlist = branched ? nullptr : probe_work_;
-  if (xchg)
-    launch_partition_sig(sig_cols(), rows_, N, nblk_sig_ + nblk_imp_, g_part_blk_, g_part_off_, g_part_tot_, st,
-                         nblk_sig_, sig_base, wspan, wjp, wlist);
-  else
-    launch_partition_sig(sig_cols(), rows_, N, nblk_sig_, g_part_blk_, g_part_off_, g_part_tot_, st, 0, sig_base,
-                         wspan, wjp, wlist);
+  uint32_t* wlist = branched ? nullptr : s.probe_work;
+  launch_partition_sig(sig_cols(buf), s.rows, N, nblk_sig_ + (xchg ? nblk_imp_ : 0), g_part_blk_, g_part_off_,
+                       g_part_tot_, st, xchg ? nblk_sig_ : 0, sig_base, wspan, wjp, wlist);
   if (branched) {  // the work list needs the signal bases just recorded; then join
     HIPCHECK(hipStreamWaitEvent(side_, ev_sigbase_, 0));
-    launch_probe_work(s_part_base_, sig_cols(), jp_, probe_work_, side_);
+    launch_probe_work(s.s_part_base, sig_cols(buf), jp_, s.probe_work, side_);
     HIPCHECK(hipEventRecord(ev_spans_, side_));
     HIPCHECK(hipStreamWaitEvent(st, ev_spans_, 0));  // spans sorted, work list built
   }
 }
 
-void WindowEngine::run_join_back(int b, int n_groups, bool with_labels, bool learn, hipStream_t st) {
-  set_buffer(b);
-  uint8_t* in = in_dev_[b];
-  const int* counts = reinterpret_cast<const int*>(in);
-  const int32_t* labels = reinterpret_cast<const int32_t*>(in + kHeadBytes);
+// Part 2, second half: join (this window's spans x every generation's visible rows) ->
+// posterior -> packet.
+void WindowEngine::run_join_back(const Buf& buf, int n_groups, bool with_labels, bool learn, hipStream_t st) {
+  const BufSet& s = *buf.set;
+  const ResultViewT<uint8_t>& r = buf.res;
+  const int* counts = buf.counts();
+  const int32_t* labels = reinterpret_cast<const int32_t*>(buf.in + kHeadBytes);
   const int S = cfg_.span_cap, G = cfg_.group_cap;
-  launch_probe(span_cols(), s_items_, s_part_base_, sig_cols(), S, jp_, top3_, cnt_, n_groups, gsum_, gcnt_, dbg_,
-               probe_work_, s_pre_, st);
-  launch_finalize(counts + 1, S, top3_, cnt_, sig_cols(), span_cols(), jp_, nullptr, attrs_, conf_, kernel_ms_,
-                  n_groups, gsum_, gcnt_, feat_, dbg_, st);
+  launch_probe(span_cols(buf), s.s_items, s.s_part_base, sig_cols(buf), S, jp_, s.top3, s.cnt, n_groups, s.gsum, s.gcnt,
+               s.dbg, s.probe_work, s.s_pre, st);
+  launch_finalize(counts + 1, S, s.top3, s.cnt, sig_cols(buf), span_cols(buf), jp_, nullptr, attrs_, conf_, kernel_ms_,
+                  n_groups, s.gsum, s.gcnt, r.feat, s.dbg, st);
   const PosteriorModel* pm = reinterpret_cast<const PosteriorModel*>(model_dev_);
   if (learn)
-    launch_posterior_stats(feat_, counts + 2, G, pm, with_labels ? labels : nullptr, post_, pred_, gconf_, evbits_,
-                           confusion_, labels, nullptr, stats_, stats_count_, st, app_dev_, app_);
+    launch_posterior_stats(r.feat, counts + 2, G, pm, with_labels ? labels : nullptr, r.post, r.pred, r.gconf, r.evbits,
+                           s.confusion, labels, nullptr, s.stats, s.stats_count, st, app_dev_, r.app);
   else
-    launch_posterior(feat_, counts + 2, G, pm, with_labels ? labels : nullptr, post_, pred_, gconf_, evbits_,
-                     confusion_, st, app_dev_, app_);
+    launch_posterior(r.feat, counts + 2, G, pm, with_labels ? labels : nullptr, r.post, r.pred, r.gconf, r.evbits,
+                     s.confusion, st, app_dev_, r.app);
   if (!comm_) {  // one GPU: the whole tail here (see k_window_end)
-    const size_t res16 = (res_bytes_ + 15) / 16;
+    const size_t res16 = (result_bytes() + 15) / 16;
     const int g = (int)std::max<size_t>((kPacketLen + 255) / 256, std::min<size_t>(64, (res16 + 255) / 256));
-    hipLaunchKernelGGL(k_window_end, dim3(g), dim3(256), 0, st, hist_, status_, misc_, dbg_, confusion_, stats_,
-                       stats_count_, ring_state_, packet_dev_[b], totals_, packet_host_[b],
-                       reinterpret_cast<const uint4*>(res_dev_[b]), reinterpret_cast<uint4*>(res_host_[b]), res16);
+    hipLaunchKernelGGL(k_window_end, dim3(g), dim3(256), 0, st, s.hist, s.status, s.misc, s.dbg, s.confusion, s.stats,
+                       s.stats_count, s.ring_state, buf.packet_dev, totals_, buf.packet_host,
+                       reinterpret_cast<const uint4*>(buf.res_dev), reinterpret_cast<uint4*>(buf.res_host), res16);
     return;
   }
-  hipLaunchKernelGGL(k_pack, dim3((kPacketLen + 255) / 256), dim3(256), 0, st, hist_, status_, misc_, dbg_, confusion_,
-                     stats_, stats_count_, ring_state_, packet_dev_[b]);
+  hipLaunchKernelGGL(k_pack, dim3((kPacketLen + 255) / 256), dim3(256), 0, st, s.hist, s.status, s.misc, s.dbg,
+                     s.confusion, s.stats, s.stats_count, s.ring_state, buf.packet_dev);
 }
 
 // The span side of the chain: decode, partition, span sort (inputs: the span DMA and the reset
 // accumulators only).
-void WindowEngine::run_spans(int b, hipStream_t st) {
-  set_buffer(b);
-  uint8_t* in = in_dev_[b];
-  const int* counts = reinterpret_cast<const int*>(in);
+void WindowEngine::run_spans(const Buf& buf, hipStream_t st) {
+  const BufSet& s = *buf.set;
+  const int* counts = buf.counts();
   const int S = cfg_.span_cap, G = cfg_.group_cap;
-  const SpanMap sm{1, sli_, G, cfg_.ttft_slo_ms, cfg_.shard_rank, cfg_.shard_world, gen_, app_, late_};
-  launch_decode_spans(in + off_span_, counts + 1, S, span_cols(), s_part_blk_, ctx_tab_, (int)kCtxRows, st, &sm);
-  launch_partition(s_part_, counts + 1, S, nblk_span_, s_part_blk_, s_part_off_, s_part_tot_, s_part_base_, s_items_,
+  const SpanMap sm{1, buf.res.sli, G, cfg_.ttft_slo_ms, cfg_.shard_rank, cfg_.shard_world,
+                   s.gen, buf.res.app, buf.res.late};
+  launch_decode_spans(buf.in + off_span_, counts + 1, S, span_cols(buf), s_part_blk_, ctx_tab_, (int)kCtxRows, st, &sm);
+  launch_partition(s.s_part, counts + 1, S, nblk_span_, s_part_blk_, s_part_off_, s_part_tot_, s.s_part_base, s.s_items,
                    st);
-  launch_span_sort(span_cols(), s_items_, s_part_base_, s_pre_, st);
+  launch_span_sort(span_cols(buf), s.s_items, s.s_part_base, s.s_pre, st);
 }
 
-// Fork from `st` (after k_window_begin): the span side on side_. run_part2 continues the branch
-// once the signal side's partition bases exist -- the probe work list reads both sides' bases
-// and time ranges -- and joins it before the probe (ev_spans_). Native 64-byte spans never read
-// the context table, so the branch does not wait for k_ring_defs.
-void WindowEngine::run_span_branch(int b, hipStream_t st) {
+// Fork from `st` (after k_window_begin): the span side on side_. run_join_front continues the
+// branch once the signal side's partition bases exist -- the probe work list reads both sides'
+// bases and time ranges -- and joins it before the probe (ev_spans_). Native 64-byte spans never
+// read the context table, so the branch does not wait for k_ring_defs.
+void WindowEngine::run_span_branch(const Buf& buf, hipStream_t st) {
   HIPCHECK(hipEventRecord(ev_fork_, st));
   HIPCHECK(hipStreamWaitEvent(side_, ev_fork_, 0));
-  run_spans(b, side_);
+  run_spans(buf, side_);
 }
 
 // Launch a chain part eagerly, or through its captured graph (captured on the buffer's second
 // use; the first use runs eagerly so lazily initialised state is out of the capture).
-void WindowEngine::launch_part(int part, int b, int n_groups, bool with_labels, bool learn, bool xchg) {
+void WindowEngine::launch_part(Stage part, const Buf& buf, int n_groups, bool with_labels, bool learn) {
+  // the stream the part runs (and is captured) on
+  hipStream_t cs = part == Stage::XchgSpans ? side_ : part == Stage::Front ? front_ : compute_;
   auto run = [&] {
-    if (part == 0) {  // the whole window in one graph (no exchange)
-      run_part1(b, compute_, false);
-      run_part2(b, n_groups, with_labels, learn, compute_, false);
-    } else if (part == 1) {
-      run_part1(b, compute_, xchg);
-    } else if (part == 2) {
-      run_part2(b, n_groups, with_labels, learn, compute_, xchg);
-    } else if (part == 3) {  // the exchange path's span side (xspan_)
-      run_spans(b, side_);
-    } else if (part == 4) {  // the exchange path's window head (xspan_)
-      run_begin(b, compute_);
-    } else if (part == 5) {  // overlapped windows: the front stage, on front_
-      run_part1(b, front_, false);
-      run_join_front(b, front_, false);
-    } else {  // part 6, overlapped windows: the back stage
-      run_join_back(b, n_groups, with_labels, learn, compute_);
+    switch (part) {
+      case Stage::Window:  // the whole window in one graph (no exchange)
+        run_part1(buf, cs, false);
+        run_join_front(buf, cs, false);
+        return run_join_back(buf, n_groups, with_labels, learn, cs);
+      case Stage::Records: return run_part1(buf, cs, true);
+      case Stage::Join:
+        run_join_front(buf, cs, true);
+        return run_join_back(buf, n_groups, with_labels, learn, cs);
+      case Stage::XchgSpans: return run_spans(buf, cs);
+      case Stage::XchgHead: return run_begin(buf, cs);
+      case Stage::Front:
+        run_part1(buf, cs, false);
+        return run_join_front(buf, cs, false);
+      case Stage::Back: return run_join_back(buf, n_groups, with_labels, learn, cs);
     }
   };
-  hipStream_t cs = part == 3 ? side_ : part == 5 ? front_ : compute_;  // the stream the part is captured on
   if (!cfg_.use_graphs) return run();
   // the front stage does not depend on the incident groups, the labels or the learning flag
-  auto key = part == 5 ? std::make_tuple(b * 8 + part, 0, false, false)
-                       : std::make_tuple(b * 8 + part, n_groups, with_labels, learn);
+  const int slot = buf.b * kStageSlots + (int)part;
+  auto key = part == Stage::Front ? std::make_tuple(slot, 0, false, false)
+                                  : std::make_tuple(slot, n_groups, with_labels, learn);
   auto it = graphs_.find(key);
-  if (it == graphs_.end() && !warm_[b * 8 + part]) {
+  if (it == graphs_.end() && !warm_[slot]) {
     run();
-    warm_[b * 8 + part] = true;
+    warm_[slot] = true;
     return;
   }
   if (it == graphs_.end()) {
@@ -690,8 +612,21 @@ void WindowEngine::launch_part(int part, int b, int n_groups, bool with_labels, 
   HIPCHECK(hipGraphLaunch(it->second, cs));
 }
 
+void WindowEngine::merge_remote(const Buf& buf, const uint8_t* blocks, size_t stride, int world, int me,
+                                hipStream_t st) {
+  launch_remote_merge(blocks, stride, world, me, buf.imp, buf.remote_n, (uint32_t)cfg_.import_cap, cfg_.xchg_cap, st,
+                      buf.set->dbg + kDbgXchgDropped);
+  launch_window_rows(buf.counts(), buf.remote_n, n_rows_, buf.set->rows, buf.set->gen, st);
+}
+
+void WindowEngine::refit(const double* add) {
+  launch_refit_nb(stats_acc_, add, p0_, cfg_.alpha, cfg_.prior_pseudo, cfg_.n_dom,
+                  reinterpret_cast<PosteriorModel*>(model_dev_), compute_, cfg_.inv_temp, cfg_.min_count,
+                  p0_ + kSlots * 16, cfg_.cap_dom, cfg_.lik_ceil);
+}
+
 void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bool learn) {
-  const auto t0 = std::chrono::steady_clock::now();
+  Lap whole;
   if (k != submitted_) throw std::invalid_argument("windows must be submitted in order");
   const int n_groups = in.n_groups;
   if (n_groups < 0 || n_groups > cfg_.group_cap) throw std::invalid_argument("n_groups exceeds group capacity");
@@ -707,19 +642,18 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   const size_t n_k = kb / kRecStride * kBatchSlots, n_u = ub / in.user_rec, n_s = sb / 64;
   if (n_k + n_u > (size_t)cfg_.sig_cap || n_u > (size_t)cfg_.user_cap || n_s > (size_t)cfg_.span_cap)
     throw std::invalid_argument("window exceeds the engine's capacity (events / user records / spans)");
-  const int b = (int)(k % nb_);
+  Buf& buf = bufs_[k % nb_];
   // host back-pressure: at most max_ahead windows queued beyond the one computing
-  const auto tw = std::chrono::steady_clock::now();
-  if (k >= max_ahead_) HIPCHECK(hipEventSynchronize(compute_done_[(k - max_ahead_) % nb_]));
-  // the pinned head / staging of buffer b were last read by the DMAs of window k - nb
+  Lap phase;
+  if (k >= max_ahead_) HIPCHECK(hipEventSynchronize(bufs_[(k - max_ahead_) % nb_].compute_done));
+  // the pinned head / staging of the buffer were last read by the DMAs of window k - nb
   if (k >= nb_) {
-    HIPCHECK(hipEventSynchronize(h2d_done_[b]));
-    HIPCHECK(hipEventSynchronize(h2d_part_[b]));
-    HIPCHECK(hipEventSynchronize(head_done_[b]));
+    HIPCHECK(hipEventSynchronize(buf.h2d_done));
+    HIPCHECK(hipEventSynchronize(buf.h2d_part));
+    HIPCHECK(hipEventSynchronize(buf.head_done));
   }
-  wait_us_ += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count();
-  const auto td = std::chrono::steady_clock::now();
-  int32_t* c = reinterpret_cast<int32_t*>(head_host_[b]);
+  phase(wait_us_);
+  int32_t* c = reinterpret_cast<int32_t*>(buf.head_host);
   std::memset(c, 0, kHeadBytes);
   c[0] = (int32_t)(n_k + n_u);
   c[1] = (int32_t)n_s;
@@ -733,154 +667,136 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
     c[9 + 2 * (q - 1)] = (int32_t)(uint32_t)((uint64_t)in.bases[q] >> 32);
   }
   c[15] = (int32_t)n_k;
-  int32_t* lab = reinterpret_cast<int32_t*>(head_host_[b] + kHeadBytes);
+  int32_t* lab = reinterpret_cast<int32_t*>(buf.head_host + kHeadBytes);
   for (int g = 0; g < cfg_.group_cap; ++g) lab[g] = (in.labels && g < n_groups) ? in.labels[g] : -1;
   // DMAs once window k - nb (the device block's previous reader) computed: the BPF ring's
   // bytes, the user-space records and the spans, back to back on the copy stream (or over two
   // streams with MISLO_COPY_STREAMS=2); the head is loaded on the compute stream (below).
-  HIPCHECK(hipStreamWaitEvent(copy_, compute_done_[b], 0));
-  HIPCHECK(hipStreamWaitEvent(copy2_, compute_done_[b], 0));
-  HIPCHECK(hipEventRecord(t_start_[b], copy_));
-  uint8_t* dst = in_dev_[b];
+  HIPCHECK(hipStreamWaitEvent(copy_, buf.compute_done, 0));
+  HIPCHECK(hipStreamWaitEvent(copy2_, buf.compute_done, 0));
+  HIPCHECK(hipEventRecord(buf.t_start, copy_));
   size_t st_off = 0;
-  auto lap = [](std::chrono::steady_clock::time_point& t, double& acc) {
-    const auto n = std::chrono::steady_clock::now();
-    acc += std::chrono::duration<double, std::micro>(n - t).count();
-    t = n;
-  };
-  auto tq = std::chrono::steady_clock::now();
-  dma(in.kernel, dst + off_kern_, kern_bytes(), staging_[b], st_off, copy_);
-  lap(tq, split_us_[0]);
-  lap(tq, split_us_[1]);
-  dma(in.user, dst + off_user_, 64 * (size_t)cfg_.user_cap, staging_[b], st_off, copy2_);
-  lap(tq, split_us_[2]);
-  dma(in.spans, dst + off_span_, 64 * (size_t)cfg_.span_cap, staging_[b], st_off, copy2_);
-  lap(tq, split_us_[3]);
-  HIPCHECK(hipEventRecord(h2d_part_[b], copy2_));
-  HIPCHECK(hipEventRecord(h2d_done_[b], copy_));
-  HIPCHECK(hipEventRecord(t_copy_end_[b], copy2_));
-  const auto te = std::chrono::steady_clock::now();
-  dma_us_ += std::chrono::duration<double, std::micro>(te - td).count();
+  Lap part;  // DMA issue: ring bytes, head (nothing: not on the copy stream), user records, spans
+  dma(in.kernel, buf.in + off_kern_, kern_bytes(), buf.staging, st_off, copy_);
+  part(split_us_[0]);
+  part(split_us_[1]);
+  dma(in.user, buf.in + off_user_, 64 * (size_t)cfg_.user_cap, buf.staging, st_off, copy2_);
+  part(split_us_[2]);
+  dma(in.spans, buf.in + off_span_, 64 * (size_t)cfg_.span_cap, buf.staging, st_off, copy2_);
+  part(split_us_[3]);
+  HIPCHECK(hipEventRecord(buf.h2d_part, copy2_));
+  HIPCHECK(hipEventRecord(buf.h2d_done, copy_));
+  HIPCHECK(hipEventRecord(buf.t_copy_end, copy2_));
+  phase(dma_us_);
   // the stream of the window's head and front half: front_ with overlapped windows (never with
   // the exchange: overlap_ is off for an engine sized for it or holding a communicator)
   hipStream_t fs = overlap_ ? front_ : compute_;
-  HIPCHECK(hipStreamWaitEvent(fs, h2d_done_[b], 0));
-  HIPCHECK(hipStreamWaitEvent(fs, h2d_part_[b], 0));
+  HIPCHECK(hipStreamWaitEvent(fs, buf.h2d_done, 0));
+  HIPCHECK(hipStreamWaitEvent(fs, buf.h2d_part, 0));
   // overlapped: the front stage of window k starts once the back stage of window k - 2 ended. It
   // overwrites the generation slot that stage probed as its oldest, and (two buffers) the buffer
   // set and the head that stage read; with it at most one window's back stage runs beside a front.
-  if (overlap_ && k >= 2) HIPCHECK(hipStreamWaitEvent(fs, compute_done_[(k - 2) % nb_], 0));
-  HIPCHECK(hipStreamWaitEvent(compute_, comm_done_[b], 0));  // packet b no longer reduced / read
+  if (overlap_ && k >= 2) HIPCHECK(hipStreamWaitEvent(fs, bufs_[(k - 2) % nb_].compute_done, 0));
+  HIPCHECK(hipStreamWaitEvent(compute_, buf.comm_done, 0));  // the buffer's packet no longer reduced / read
   const bool injected = !inject_.empty();
   if (injected) {
     // rows as the other GPUs would have delivered them (tests, replays): on the device before the
     // window's timed chain (the all-gather they stand for is not the chain's), after window k-1's
-    // merge read the receive buffer (compute stream order); the host copy is released here
+    // merge read the receive buffer (compute stream order); the host copy is released below
     HIPCHECK(hipMemcpyAsync(xrecv_, inject_.data(), inject_.size(), hipMemcpyHostToDevice, compute_));
     HIPCHECK(hipStreamSynchronize(compute_));
   }
-  HIPCHECK(hipEventRecord(t_comp0_[b], fs));
+  HIPCHECK(hipEventRecord(buf.t_comp0, fs));
   // the head (counts, epoch bases, labels: < 1 KiB) by a kernel load from pinned host memory on
   // the compute stream (the front stream with overlapped windows): a small hipMemcpyAsync H2D is
   // written by the host through the BAR and blocks this thread, and a kernel on the copy stream
   // put ~25 us of queue hand-offs between the window's DMAs (measured); the compute stream has
   // the slack
-  to_host(head_host_[b], dst, off_kern_, fs);
-  HIPCHECK(hipEventRecord(head_done_[b], fs));
+  to_host(buf.head_host, buf.in, off_kern_, fs);
+  HIPCHECK(hipEventRecord(buf.head_done, fs));
   if (cfg_.device_refit && k >= nb_) {
-    // fold window k - nb's all-reduced statistics (packet b) and refit before window k: a
-    // deterministic prequential lag of nb, identical on every rank
-    launch_refit_nb(stats_acc_, packet_dev_[b] + kStatsOff, p0_, cfg_.alpha, cfg_.prior_pseudo, cfg_.n_dom,
-                    reinterpret_cast<PosteriorModel*>(model_dev_), compute_, cfg_.inv_temp, cfg_.min_count,
-                    p0_ + kSlots * 16, cfg_.cap_dom, cfg_.lik_ceil);
+    // fold window k - nb's all-reduced statistics (the buffer's last packet) and refit before
+    // window k: a deterministic prequential lag of nb, identical on every rank
+    refit(buf.packet_dev + kStatsOff);
     ++folded_;
   }
   const bool xchg = exchange() || injected;
-  const auto tl = std::chrono::steady_clock::now();
-  pre_us_ += std::chrono::duration<double, std::micro>(tl - te).count();
+  phase(pre_us_);
   if (overlap_) {
     if (xchg) throw std::logic_error("the exchange path does not run with overlapped windows");
     // two stages, two graphs: the front on front_, the back on compute_ once the front ended
-    launch_part(5, b, n_groups, with_labels, learn, false);
-    HIPCHECK(hipEventRecord(front_done_[b], front_));
-    HIPCHECK(hipStreamWaitEvent(compute_, front_done_[b], 0));
-    launch_part(6, b, n_groups, with_labels, learn, false);
+    launch_part(Stage::Front, buf, n_groups, with_labels, learn);
+    HIPCHECK(hipEventRecord(buf.front_done, front_));
+    HIPCHECK(hipStreamWaitEvent(compute_, buf.front_done, 0));
+    launch_part(Stage::Back, buf, n_groups, with_labels, learn);
   } else if (!xchg) {
-    launch_part(0, b, n_groups, with_labels, learn, false);
+    launch_part(Stage::Window, buf, n_groups, with_labels, learn);
   } else {
     if (xspan_) {
       // the window head, then the span side (decode, partition, sort: it reads only the span DMA
       // and the reset accumulators) on side_ while part 1 decodes the records; joined before part 2
-      launch_part(4, b, n_groups, with_labels, learn, true);
+      launch_part(Stage::XchgHead, buf, n_groups, with_labels, learn);
       HIPCHECK(hipEventRecord(ev_fork_, compute_));
       HIPCHECK(hipStreamWaitEvent(side_, ev_fork_, 0));
-      launch_part(3, b, n_groups, with_labels, learn, true);
+      launch_part(Stage::XchgSpans, buf, n_groups, with_labels, learn);
       HIPCHECK(hipEventRecord(ev_spans_, side_));
     }
-    launch_part(1, b, n_groups, with_labels, learn, true);
+    launch_part(Stage::Records, buf, n_groups, with_labels, learn);
     // the exchange sits between the window's two halves: every GPU's trace rows of THIS window
     if (injected) {  // rows as the other GPUs would have delivered them (copied above)
-      launch_remote_merge(xrecv_, inject_stride_, inject_world_, inject_me_, imp_[b], remote_n_ + b,
-                          (uint32_t)cfg_.import_cap, cfg_.xchg_cap, compute_, dbg_ + kDbgXchgDropped);
+      merge_remote(buf, xrecv_, inject_stride_, inject_world_, inject_me_, compute_);
       inject_.clear();
-      launch_window_rows(reinterpret_cast<const int*>(in_dev_[b]), remote_n_ + b, n_rows_, rows_, gen_, compute_);
     } else if (xcomm_) {
       // on the compute stream, over the exchange's own communicator (each communicator is used
       // on one stream only, so each keeps one issue order on every rank): part 2 follows the
       // merge in stream order, with no hand-off between hardware queues on the window's critical
       // path (each such hop idled the compute queue 20-45 us, profiles/r5_multigpu/)
       NCCLCHECK(ncclAllGather(xsend_, xrecv_, xstride_, ncclUint8, xcomm_, compute_));
-      launch_remote_merge(xrecv_, xstride_, world_, rank_, imp_[b], remote_n_ + b, (uint32_t)cfg_.import_cap,
-                          cfg_.xchg_cap, compute_, dbg_ + kDbgXchgDropped);
-      launch_window_rows(reinterpret_cast<const int*>(in_dev_[b]), remote_n_ + b, n_rows_, rows_, gen_, compute_);
+      merge_remote(buf, xrecv_, xstride_, world_, rank_, compute_);
     } else {
       // MISLO_XCHG_STREAM=comm: the exchange on the comm stream with the window's other
       // collectives: the compute stream hands over after part 1 and waits for the merge
-      HIPCHECK(hipEventRecord(xchg_done_[b], compute_));
-      HIPCHECK(hipStreamWaitEvent(comm_stream_, xchg_done_[b], 0));
+      HIPCHECK(hipEventRecord(buf.xchg_done, compute_));
+      HIPCHECK(hipStreamWaitEvent(comm_stream_, buf.xchg_done, 0));
       NCCLCHECK(ncclAllGather(xsend_, xrecv_, xstride_, ncclUint8, comm_, comm_stream_));
-      launch_remote_merge(xrecv_, xstride_, world_, rank_, imp_[b], remote_n_ + b, (uint32_t)cfg_.import_cap,
-                          cfg_.xchg_cap, comm_stream_, dbg_ + kDbgXchgDropped);
-      launch_window_rows(reinterpret_cast<const int*>(in_dev_[b]), remote_n_ + b, n_rows_, rows_, gen_, comm_stream_);
-      HIPCHECK(hipEventRecord(xchg_done_[b], comm_stream_));
-      HIPCHECK(hipStreamWaitEvent(compute_, xchg_done_[b], 0));
+      merge_remote(buf, xrecv_, xstride_, world_, rank_, comm_stream_);
+      HIPCHECK(hipEventRecord(buf.xchg_done, comm_stream_));
+      HIPCHECK(hipStreamWaitEvent(compute_, buf.xchg_done, 0));
     }
     if (xspan_) HIPCHECK(hipStreamWaitEvent(compute_, ev_spans_, 0));
-    launch_part(2, b, n_groups, with_labels, learn, true);
+    launch_part(Stage::Join, buf, n_groups, with_labels, learn);
   }
-  const auto tt = std::chrono::steady_clock::now();
-  launch_us_ += std::chrono::duration<double, std::micro>(tt - tl).count();
+  phase(launch_us_);
   // per-incident results of this window (the buffers are reused by the next window); one GPU:
   // copied by the graph's k_window_end
-  if (comm_) to_host(res_dev_[b], res_host_[b], res_bytes_, compute_);
-  HIPCHECK(hipEventRecord(t_comp1_[b], compute_));
-  HIPCHECK(hipEventRecord(compute_done_[b], compute_));
-  HIPCHECK(hipStreamWaitEvent(comm_stream_, compute_done_[b], 0));
+  const size_t res_bytes = result_bytes();
+  if (comm_) to_host(buf.res_dev, buf.res_host, res_bytes, compute_);
+  HIPCHECK(hipEventRecord(buf.t_comp1, compute_));
+  HIPCHECK(hipEventRecord(buf.compute_done, compute_));
+  HIPCHECK(hipStreamWaitEvent(comm_stream_, buf.compute_done, 0));
   if (comm_) {
     // one group: the node-wide packet and the node-wide incident list. The ring accounting at
     // the packet's tail stays this GPU's own (each GPU is a consumer of its rings: its first busy
     // record, its records), so it is left out of the sum.
     NCCLCHECK(ncclGroupStart());
-    NCCLCHECK(ncclAllReduce(packet_dev_[b], packet_dev_[b], kPacketLen - kPacketRing, ncclFloat64, ncclSum, comm_,
+    NCCLCHECK(ncclAllReduce(buf.packet_dev, buf.packet_dev, kPacketLen - kPacketRing, ncclFloat64, ncclSum, comm_,
                             comm_stream_));
-    NCCLCHECK(ncclAllGather(res_dev_[b], res_all_dev_[b], res_bytes_, ncclUint8, comm_, comm_stream_));
+    NCCLCHECK(ncclAllGather(buf.res_dev, buf.res_all_dev, res_bytes, ncclUint8, comm_, comm_stream_));
     NCCLCHECK(ncclGroupEnd());
-    to_host(res_all_dev_[b], res_all_host_[b], res_bytes_ * world_, comm_stream_);
+    to_host(buf.res_all_dev, buf.res_all_host, res_bytes * world_, comm_stream_);
+    hipLaunchKernelGGL(k_accumulate, dim3((kPacketLen + 255) / 256), dim3(256), 0, comm_stream_, buf.packet_dev,
+                       totals_, kPacketLen, buf.packet_host);
   }
-  if (comm_)
-    hipLaunchKernelGGL(k_accumulate, dim3((kPacketLen + 255) / 256), dim3(256), 0, comm_stream_, packet_dev_[b],
-                       totals_, kPacketLen, packet_host_[b]);
-  HIPCHECK(hipEventRecord(t_end_[b], comm_stream_));
-  HIPCHECK(hipEventRecord(comm_done_[b], comm_stream_));
+  HIPCHECK(hipEventRecord(buf.t_end, comm_stream_));
+  HIPCHECK(hipEventRecord(buf.comm_done, comm_stream_));
   ++submitted_;
-  const auto t1 = std::chrono::steady_clock::now();
-  tail_us_ += std::chrono::duration<double, std::micro>(t1 - tt).count();
-  issue_us_ += std::chrono::duration<double, std::micro>(t1 - t0).count();
+  phase(tail_us_);
+  whole(issue_us_);
   ++issue_n_;
 }
 
 bool WindowEngine::query(int64_t k) {
-  const hipError_t e = hipEventQuery(comm_done_[k % nb_]);
+  const hipError_t e = hipEventQuery(bufs_[k % nb_].comm_done);
   if (e == hipSuccess) return true;
   if (e == hipErrorNotReady) return false;
   HIPCHECK(e);
@@ -889,43 +805,29 @@ bool WindowEngine::query(int64_t k) {
 
 void WindowEngine::wait(int64_t k) {
   if (spin_) {  // poll: no interrupt wake-up latency (flat-out benchmarking; costs a core)
-    for (;;) {
-      const hipError_t e = hipEventQuery(comm_done_[k % nb_]);
-      if (e == hipSuccess) return;
-      if (e != hipErrorNotReady) HIPCHECK(e);
+    while (!query(k)) {
     }
+    return;
   }
-  HIPCHECK(hipEventSynchronize(comm_done_[k % nb_]));
-}
-
-ResultView WindowEngine::results(int64_t k) const {
-  const uint8_t* r = res_host_[k % nb_];
-  const size_t G = cfg_.group_cap;
-  const size_t o_gconf = 16 * G * 8, o_feat = o_gconf + G * 8, o_pred = o_feat + 16 * G * 4, o_ev = o_pred + G * 4;
-  const size_t o_sli = o_ev + 16 * G * 4;
-  return ResultView{reinterpret_cast<const double*>(r), reinterpret_cast<const double*>(r + o_gconf),
-                    reinterpret_cast<const float*>(r + o_feat), reinterpret_cast<const int32_t*>(r + o_pred),
-                    reinterpret_cast<const uint32_t*>(r + o_ev), reinterpret_cast<const uint32_t*>(r + o_sli),
-                    reinterpret_cast<const uint32_t*>(r + o_sli) + 2 * G,
-                    reinterpret_cast<const uint32_t*>(r + o_sli) + 4 * G};
+  HIPCHECK(hipEventSynchronize(bufs_[k % nb_].comm_done));
 }
 
 std::vector<float> WindowEngine::copy_ms(int64_t k) {
   // [copy duration of window k, copy-engine idle time between window k-1's DMAs and k's]
-  const int b = (int)(k % nb_);
+  const Buf& buf = bufs_[k % nb_];
   float dur = 0.f, gap = -1.f;
-  HIPCHECK(hipEventSynchronize(t_copy_end_[b]));
-  HIPCHECK(hipEventElapsedTime(&dur, t_start_[b], t_copy_end_[b]));
-  if (k >= 1 && nb_ > 1) HIPCHECK(hipEventElapsedTime(&gap, t_copy_end_[(k - 1) % nb_], t_start_[b]));
+  HIPCHECK(hipEventSynchronize(buf.t_copy_end));
+  HIPCHECK(hipEventElapsedTime(&dur, buf.t_start, buf.t_copy_end));
+  if (k >= 1 && nb_ > 1) HIPCHECK(hipEventElapsedTime(&gap, bufs_[(k - 1) % nb_].t_copy_end, buf.t_start));
   return {dur, gap};
 }
 
 std::pair<float, float> WindowEngine::window_ms(int64_t k) {
-  const int b = (int)(k % nb_);
+  const Buf& buf = bufs_[k % nb_];
   float total = 0.f, comp = 0.f;
-  HIPCHECK(hipEventSynchronize(t_end_[b]));
-  HIPCHECK(hipEventElapsedTime(&total, t_start_[b], t_end_[b]));
-  HIPCHECK(hipEventElapsedTime(&comp, t_comp0_[b], t_comp1_[b]));
+  HIPCHECK(hipEventSynchronize(buf.t_end));
+  HIPCHECK(hipEventElapsedTime(&total, buf.t_start, buf.t_end));
+  HIPCHECK(hipEventElapsedTime(&comp, buf.t_comp0, buf.t_comp1));
   return {total, comp};
 }
 
@@ -964,11 +866,7 @@ void WindowEngine::set_refit(double alpha, double prior_pseudo, double inv_temp,
   cfg_.min_count = min_count;
 }
 
-void WindowEngine::refit_now() {
-  launch_refit_nb(stats_acc_, nullptr, p0_, cfg_.alpha, cfg_.prior_pseudo, cfg_.n_dom,
-                  reinterpret_cast<PosteriorModel*>(model_dev_), compute_, cfg_.inv_temp, cfg_.min_count,
-                    p0_ + kSlots * 16, cfg_.cap_dom, cfg_.lik_ceil);
-}
+void WindowEngine::refit_now() { refit(nullptr); }
 
 void WindowEngine::score_features(const float* feat, int n, const int32_t* labels, double* post, int32_t* pred,
                                   double* conf, uint32_t* evbits, uint32_t* confusion, const uint32_t* app_cnt) {
@@ -981,8 +879,7 @@ void WindowEngine::score_features(const float* feat, int n, const int32_t* label
   const size_t o_pred = o_post + (size_t)n * 16 * 8, o_conf = (o_pred + (size_t)n * 4 + 63) & ~size_t(63);
   const size_t o_ev = o_conf + (size_t)n * 8, o_cm = o_ev + (size_t)n * 16 * 4, o_app = o_cm + 16 * 16 * 4;
   const size_t bytes = o_app + (size_t)n * 2 * 4;
-  uint8_t* d = dalloc<uint8_t>(bytes);
-  HIPCHECK(hipMemset(d, 0, bytes));
+  uint8_t* d = dalloc<uint8_t>(bytes, true);
   HIPCHECK(hipMemcpy(d, feat, o_n, hipMemcpyHostToDevice));
   HIPCHECK(hipMemcpy(d + o_n, &n, sizeof(int), hipMemcpyHostToDevice));
   if (labels) HIPCHECK(hipMemcpy(d + o_lab, labels, (size_t)n * 4, hipMemcpyHostToDevice));
@@ -999,7 +896,7 @@ void WindowEngine::score_features(const float* feat, int n, const int32_t* label
   HIPCHECK(hipMemcpy(conf, d + o_conf, (size_t)n * 8, hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(evbits, d + o_ev, (size_t)n * 16 * 4, hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(confusion, d + o_cm, 16 * 16 * 4, hipMemcpyDeviceToHost));
-  HIPCHECK(hipFree(d));
+  own_.free_dev(d);
 }
 
 void WindowEngine::set_pods(const uint32_t* pods, const uint32_t* svcnode, size_t n) {
@@ -1027,10 +924,10 @@ std::vector<int64_t> WindowEngine::import_state() {
   unsigned long long tmax = 0;
   GenMeta g{};
   std::vector<uint32_t> r(nb_);
-  set_buffer(submitted_ ? (int)((submitted_ - 1) % nb_) : 0);  // the latest window's set
-  HIPCHECK(hipMemcpy(rows, rows_, sizeof(rows), hipMemcpyDeviceToHost));
+  const BufSet& s = *bufs_[submitted_ ? (submitted_ - 1) % nb_ : 0].set;  // the latest window's set
+  HIPCHECK(hipMemcpy(rows, s.rows, sizeof(rows), hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(&tmax, tmax_, 8, hipMemcpyDeviceToHost));
-  HIPCHECK(hipMemcpy(&g, gen_, sizeof(g), hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(&g, s.gen, sizeof(g), hipMemcpyDeviceToHost));
   HIPCHECK(hipMemcpy(r.data(), remote_n_, 4 * nb_, hipMemcpyDeviceToHost));
   // rows[0..1], tmax, generations, current slot, windows held, per age: cut-off and rows, per
   // buffer: other GPUs' rows
@@ -1053,7 +950,7 @@ void WindowEngine::inject_remote(const void* blocks, size_t stride, int world, i
   }
   if (stride * world > xrecv_bytes_) {
     sync();
-    if (xrecv_) HIPCHECK(hipFree(xrecv_));
+    own_.free_dev(xrecv_);  // outgrown
     xrecv_ = dalloc<uint8_t>(stride * world);
     xrecv_bytes_ = stride * world;
   }
@@ -1084,26 +981,19 @@ void WindowEngine::init_comm(const ncclUniqueId& id, int rank, int world) {
     // k's compute -- so no two windows overlapped (measured with a one-rank communicator,
     // tools/rccl_overlap.py: copy-engine idle 0.65-0.75 ms per window, 1.27-1.35 ms per window
     // against 0.77 ms without a communicator). MISLO_COMM_STREAM_PRIO=0: the default priority.
-    int lo = 0, hi = 0;
-    HIPCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    const char* pv = getenv("MISLO_COMM_STREAM_PRIO");
-    if (pv && atoi(pv) == 0)
-      HIPCHECK(hipStreamCreateWithFlags(&comm_stream_, hipStreamNonBlocking));
-    else
-      HIPCHECK(hipStreamCreateWithPriority(&comm_stream_, hipStreamNonBlocking, hi));
+    comm_stream_ = mk_stream(env_int("MISLO_COMM_STREAM_PRIO", 1) != 0);
   }
   rank_ = rank;
   world_ = world;
-  for (int b = 0; b < nb_; ++b) {
-    res_all_dev_.push_back(dalloc<uint8_t>(res_bytes_ * world));
-    res_all_host_.push_back(static_cast<uint8_t*>(host_block(res_bytes_ * world)));
+  for (Buf& buf : bufs_) {
+    buf.res_all_dev = dalloc<uint8_t>(result_bytes() * world);
+    buf.res_all_host = static_cast<uint8_t*>(host_block(result_bytes() * world));
   }
   if (cfg_.xchg_cap) {
     if (world > 8) throw std::invalid_argument("the exchange is sized for <= 8 GPUs per node");
-    if (xrecv_) HIPCHECK(hipFree(xrecv_));
-    xrecv_ = dalloc<uint8_t>(xstride_ * world);
+    own_.free_dev(xrecv_);  // one sized by inject_remote
     xrecv_bytes_ = xstride_ * world;
-    HIPCHECK(hipMemset(xrecv_, 0, xrecv_bytes_));
+    xrecv_ = dalloc<uint8_t>(xrecv_bytes_, true);
     // The exchange runs on the comm stream with the window's other collectives: one communicator,
     // one stream, one issue order on every rank. MISLO_XCHG_STREAM=compute puts it on the compute
     // stream over a communicator of its own (ncclCommSplit: 0.60 against 0.62 ms per window in the
@@ -1118,7 +1008,7 @@ void WindowEngine::init_comm(const ncclUniqueId& id, int rank, int world) {
     NCCLCHECK(ncclBroadcast(d_split, d_split, 1, ncclInt32, 0, comm_, comm_stream_));
     HIPCHECK(hipStreamSynchronize(comm_stream_));
     HIPCHECK(hipMemcpy(&split, d_split, sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHECK(hipFree(d_split));
+    own_.free_dev(d_split);
     if (split) NCCLCHECK(ncclCommSplit(comm_, 0, rank, &xcomm_, nullptr));
   }
 }
@@ -1145,9 +1035,7 @@ void WindowEngine::restore(const double* stats, const void* model, size_t n, int
   if (n) {
     HIPCHECK(hipMemcpy(model_dev_, model, n, hipMemcpyHostToDevice));
   } else {  // the learned model from the restored statistics, by the device refit itself
-    launch_refit_nb(stats_acc_, nullptr, p0_, cfg_.alpha, cfg_.prior_pseudo, cfg_.n_dom,
-                    reinterpret_cast<PosteriorModel*>(model_dev_), compute_, cfg_.inv_temp, cfg_.min_count,
-                    p0_ + kSlots * 16, cfg_.cap_dom, cfg_.lik_ceil);
+    refit(nullptr);
     HIPCHECK(hipStreamSynchronize(compute_));
   }
   folded_ = folded;

@@ -96,7 +96,8 @@ def stress():
 def _run(tag, imgs, pods, overlap, use_graphs, n_buffers, cuts=None, **kw):
     """The sequence through one engine, windows staged ahead of the read-back: per window the raw
     packet and result block (copies). ``cuts``: a list receiving import_state()'s per-age
-    cut-offs after every window (drains the engine: the serial reference only)."""
+    cut-offs after every staged window (the query drains the engine, so no two windows of such
+    a run overlap in time; what it may not do is change what a later window computes)."""
     from llm_slo_ebpf_toolkit_amd.pipeline.window import RingWindowSource, WindowPipeline
 
     old = os.environ.get("MISLO_WINDOW_OVERLAP")
@@ -180,6 +181,33 @@ def test_overlapped_windows_match_oracle_and_serial_engine(stress, use_graphs, n
         assert sorted(res) == sorted(ser[j][1])
         for key in res:
             assert res[key].tobytes() == ser[j][1][key].tobytes(), (msg, key)
+
+
+@pytest.mark.parametrize("n_buffers", [2, 3])
+def test_import_state_between_windows_disturbs_no_later_window(stress, n_buffers):
+    """import_state() after every staged window of the overlapped engine (graphs on: from a
+    buffer's third use its stages are replayed, not re-run): the diagnostic reads the latest
+    window's buffer and changes nothing, so every window's packet and result arrays are the bytes
+    of the same engine run without the queries, and the per-age cut-offs it returns window by
+    window are the serial engine's."""
+    _, imgs, pods, _ = stress
+    tag = f"q{n_buffers}"
+    ser_cuts, ovl_cuts = [], []
+    _run("s" + tag, imgs, pods, False, True, n_buffers, cuts=ser_cuts)
+    plain, plain_state, _ = _run("p" + tag, imgs, pods, True, True, n_buffers)
+    asked, asked_state, graphs = _run("a" + tag, imgs, pods, True, True, n_buffers, cuts=ovl_cuts)
+    assert graphs >= 2 * n_buffers  # the stages were replayed from captured graphs
+    assert len(ovl_cuts) == len(imgs) and ovl_cuts == ser_cuts
+    # precondition: rows three windows old were visible somewhere
+    assert any(c[0] == -(1 << 63) and c[3] != INT64_MAX for c in ovl_cuts), ovl_cuts
+    assert asked_state == plain_state
+    assert len(asked) == len(plain) == len(imgs)
+    for j in range(len(imgs)):
+        msg = f"window {j} ({SEQUENCE[j]})"
+        assert asked[j][0].tobytes() == plain[j][0].tobytes(), msg
+        assert sorted(asked[j][1]) == sorted(plain[j][1])
+        for key in asked[j][1]:
+            assert asked[j][1][key].tobytes() == plain[j][1][key].tobytes(), (msg, key)
 
 
 def test_overlap_with_the_span_side_on_its_own_stream(stress, monkeypatch):
