@@ -212,6 +212,10 @@ class AgentOptions:
     # pipeline/openreq.py), not when the late first token arrives; one GPU; nothing is checkpointed
     deadline_breach: bool = False
     open_requests_cap: int = 1 << 20     # entries of the open-request table
+    # per-service TTFT distributions of every window and of a rolling horizon, from a sketch on the GPU
+    # (pipeline/slisketch.py); one GPU; nothing is checkpointed
+    ttft_distribution: bool = False
+    ttft_horizon_windows: int = 0        # windows of the rolling horizon (0: 5 minutes of windows)
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -728,6 +732,8 @@ class Agent:
                     "late": late_l[g] if g < len(late_l) else 0, "emitted": emit,
                     **({"deadline": res["deadline"][g].tolist()} if res.get("deadline") is not None
                        and g < len(res["deadline"]) else {}),
+                    **({"ttft_ms": self._ttft_row(res, g)} if res.get("ttft_n") is not None
+                       and g < len(res["ttft_n"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -754,6 +760,21 @@ class Agent:
                 fault_hypotheses=[FaultHypothesis(p.domain, p.posterior, p.evidence) for p in ranked
                                   if p.posterior >= 0.01]))
         return out
+
+    @staticmethod
+    def _ttft_row(res: dict, g: int) -> dict:
+        """Group g's TTFT distribution for the decision log (None: no record in that scope)."""
+        def ms(v):
+            v = float(v)
+            return round(v, 3) if math.isfinite(v) else None
+
+        q, qr = res["ttft_q"][g], res["ttft_q_roll"][g]  # p50, p90, p95, p99
+        return {"n": int(res["ttft_n"][g]), "p50": ms(q[0]), "p95": ms(q[2]), "p99": ms(q[3]), "p95_5m": ms(qr[2])}
+
+    def ttft_horizon(self) -> int:
+        """Windows of the TTFT sketch's rolling horizon: the flag, or the 5 minutes the burn forecast quotes."""
+        w = int(self.o.ttft_horizon_windows)
+        return w if w > 0 else max(1, int(round(300000.0 / max(float(self.o.window_ms), 1e-3))))
 
     @staticmethod
     def _retrieval_evidence(res: dict, g: int) -> List[Evidence]:
@@ -794,6 +815,8 @@ class Agent:
         self.last_results = res
         if head.get("open_requests") is not None and res.get("deadline") is not None:
             self.metrics.observe_open_requests(res["deadline"], head["open_requests"], names)
+        if head.get("ttft_sketch") is not None and res.get("ttft_n") is not None:
+            self.metrics.observe_ttft(res, head["ttft_sketch"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -902,6 +925,9 @@ class Agent:
         if o.deadline_breach and N > 1:
             raise ValueError("--deadline-breach runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the open-request corrections are applied on the host")
+        if o.ttft_distribution and N > 1:
+            raise ValueError("--ttft-distribution runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the TTFT sketch's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -946,7 +972,8 @@ class Agent:
                             pods=pods, master=("127.0.0.1", port), halo_windows=halo_windows, split=split,
                             app_image=app_model_bytes(model).tobytes() if model.app is not None else b"",
                             open_requests=int(o.open_requests_cap) if o.deadline_breach else 0,
-                            open_reorder_ms=2.0 * float(o.window_ms))
+                            open_reorder_ms=2.0 * float(o.window_ms),
+                            sli_sketch=self.ttft_horizon() if o.ttft_distribution else 0)
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

@@ -98,6 +98,23 @@ class AgentMetrics:
                                      "Open-request table events: dup_start, start_after_sli, dropped_full, expired "
                                      "(counted, never reported within the ttl), false_deadline (counted, then "
                                      "reported within the SLO).", ("reason",))
+        # the TTFT sketch (agent --ttft-distribution, pipeline/slisketch.py): every service's TTFT as
+        # the agent sees it. The name keeps it apart from the demo service's own llm_slo_ttft_ms.
+        from ..pipeline import slisketch as sk
+
+        self.ttft_hist = r.histogram("llm_slo_agent_ttft_ms",
+                                     "TTFT (ms) of the SLI records the agent counted, by service, at the "
+                                     "llm_slo_ttft_ms boundaries (exact counts and sum, built on the GPU).",
+                                     sk.EDGES, ("service",))
+        self.ttft_quantile = r.gauge("llm_slo_agent_ttft_quantile_ms",
+                                     "TTFT quantile (ms) by service from the GPU sketch (16 buckets per octave: "
+                                     "within 1/32 of the nearest-rank value); scope window = the last window, "
+                                     "rolling = the last --ttft-horizon-windows windows.",
+                                     ("service", "quantile", "scope"))
+        self.ttft_events = r.counter("llm_slo_agent_ttft_sketch_events_total",
+                                     "TTFT sketch events: invalid (a counted record with a NaN or negative TTFT, in "
+                                     "no bucket), underflow (below 0.125 ms), overflow (2^21 ms or more).",
+                                     ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -216,6 +233,24 @@ class AgentMetrics:
             self.open_requests.set(float(stats.get("live_" + state, 0)), state)
         for reason in ("dup_start", "start_after_sli", "dropped_full", "expired", "false_deadline"):
             self.open_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_ttft(self, res: dict, stats: dict, names) -> None:
+        """One window of the TTFT sketch: ``res`` carries ttft_n / ttft_sum_ms / ttft_le / ttft_q /
+        ttft_q_roll / ttft_n_roll per group (pipeline/slisketch.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.slisketch import EVENT_STATS, QUANTILE_NAMES
+
+        n, n_roll = np.asarray(res["ttft_n"]).tolist(), np.asarray(res["ttft_n_roll"]).tolist()
+        for g, cnt in enumerate(n):
+            svc = names[g] if g < len(names) else f"group-{g}"
+            if cnt:
+                self.ttft_hist.add_counts(np.asarray(res["ttft_le"][g], dtype=np.float64).tolist(),
+                                          float(res["ttft_sum_ms"][g]), svc)
+            for scope, have, q in (("window", cnt, res["ttft_q"][g]), ("rolling", n_roll[g], res["ttft_q_roll"][g])):
+                if have:  # an empty scope keeps its last value: NaN would break rate() and max()
+                    for name, v in zip(QUANTILE_NAMES, np.asarray(q, dtype=np.float64).tolist()):
+                        self.ttft_quantile.set(v, svc, name, scope)
+        for reason in EVENT_STATS:
+            self.ttft_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

@@ -81,6 +81,7 @@ class WorkerSpec:
     app_image: bytes = b""      # the application evidence model (ops/engine.py app_model_bytes); empty: off
     open_requests: int = 0      # entries of the open-request table (agent --deadline-breach); 0: off
     open_reorder_ms: float = 2000.0
+    sli_sketch: int = 0         # windows of the TTFT sketch's rolling horizon (agent --ttft-distribution); 0: off
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -94,7 +95,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     world = len(parts)
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
-                "deadline_dup"):
+                "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -163,7 +164,7 @@ class WorkerCore:
                                    xchg_cap=spec.xchg_cap, shard=(spec.rank, spec.world), engine=spec.engine,
                                    group=group, model_image=np.frombuffer(spec.model_image, dtype=np.uint8),
                                    split_rings=spec.split, open_requests=spec.open_requests,
-                                   open_reorder_ms=spec.open_reorder_ms)
+                                   open_reorder_ms=spec.open_reorder_ms, sli_sketch=spec.sli_sketch)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -283,6 +284,10 @@ class WorkerCore:
                 from ..pipeline.openreq import stats_dict
 
                 d["open_requests"] = stats_dict(pipe.open_results(k, n_groups)["stats"])
+            if pipe.sketch is not None:  # the TTFT sketch's statistics of the window
+                from ..pipeline.slisketch import stats_dict as sketch_stats
+
+                d["ttft_sketch"] = sketch_stats(pipe.sli_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

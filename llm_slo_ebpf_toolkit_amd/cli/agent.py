@@ -113,6 +113,12 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                    "only; the table is not checkpointed"),
         ("open-requests-cap", d.open_requests_cap, "--deadline-breach: entries of the open-request table (a power "
                                                    "of two)"),
+        ("ttft-distribution", False, "gpu engine: per-service TTFT distributions from a sketch on the GPU -- "
+                                     "llm_slo_agent_ttft_ms{service} at the llm_slo_ttft_ms boundaries and "
+                                     "p50/p90/p95/p99 of the window and of a rolling horizon; one GPU only; the "
+                                     "horizon is not checkpointed"),
+        ("ttft-horizon-windows", d.ttft_horizon_windows, "--ttft-distribution: windows of the rolling horizon "
+                                                         "(0 = round(300000 / window-ms): 5 minutes)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -162,6 +168,7 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         emit_recovered_requests=int(a.emit_recovered_requests),
         decision_log=a.decision_log, deadline_breach=bool(a.deadline_breach),
         open_requests_cap=int(a.open_requests_cap),
+        ttft_distribution=bool(a.ttft_distribution), ttft_horizon_windows=int(a.ttft_horizon_windows),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -11,6 +11,7 @@
 
 #include "engine.h"
 #include "openreq.h"
+#include "slisketch.h"
 
 namespace py = pybind11;
 using namespace mislo;
@@ -378,6 +379,87 @@ class PyOpenRequests {
   std::unique_ptr<OpenRequests> t_;
 };
 
+// The TTFT sketch (slisketch.h): one step per window over the same span ranges the engine gets;
+// results per step index.
+class PySliSketch {
+ public:
+  PySliSketch(int device, int span_cap, int group_cap, int windows, int n_buffers) {
+    slisketch::Config c;
+    c.device = device;
+    c.span_cap = span_cap;
+    c.group_cap = group_cap;
+    c.windows = windows;
+    c.n_buffers = n_buffers;
+    slisketch::validate(c);
+    t_ = std::make_unique<SliSketch>(c);
+  }
+  SliSketch& t() {
+    if (!t_) throw std::logic_error("ttft sketch closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    SliSketch& sk = t();
+    py::gil_scoped_release nogil;
+    return sk.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    SliSketch& sk = t();
+    if (n_groups < 0 || n_groups > sk.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = sk.results(i);
+    }
+    const slisketch::Layout& l = sk.result_layout();
+    const py::ssize_t G = n_groups;
+    std::vector<uint64_t> sum((size_t)G);
+    for (py::ssize_t g = 0; g < G; ++g)
+      sum[(size_t)g] = (uint64_t)r[l.sum + 2 * g] | ((uint64_t)r[l.sum + 2 * g + 1] << 32);
+    py::dict d;
+    d["n"] = copy_array(r + l.n, {G});
+    d["sum_milli"] = copy_array(sum.data(), {G});
+    d["le"] = copy_array(r + l.le, {G, slisketch::kLe});
+    d["q_win"] = copy_array(r + l.q_win, {G, slisketch::kQuantiles});
+    d["n_roll"] = copy_array(r + l.n_roll, {G});
+    d["q_roll"] = copy_array(r + l.q_roll, {G, slisketch::kQuantiles});
+    d["stats"] = copy_array(r + l.stats, {slisketch::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::pair<float, float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms.first, ms.second);
+  }
+  py::array_t<uint32_t> rolling() { return rows(true); }
+  py::array_t<uint32_t> window_hist() { return rows(false); }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  py::array_t<uint32_t> rows(bool roll) {
+    SliSketch& sk = t();
+    std::vector<uint32_t> h;
+    {
+      py::gil_scoped_release nogil;
+      h = roll ? sk.rolling() : sk.window_hist();
+    }
+    return copy_array(h.data(), {sk.config().group_cap, slisketch::kK});
+  }
+  std::unique_ptr<SliSketch> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -422,6 +504,27 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("entries", &PyOpenRequests::entries)
       .def("sync", &PyOpenRequests::sync)
       .def("close", &PyOpenRequests::close);
+  m.attr("SLISKETCH_K") = slisketch::kK;
+  m.attr("SLISKETCH_LO_KEY") = slisketch::kLo;
+  m.attr("SLISKETCH_STATS") = (int)slisketch::kStats;
+  {
+    py::list edges, q;
+    for (int j = 0; j < slisketch::kEdges; ++j) edges.append((double)slisketch::le_edge(j));
+    for (int j = 0; j < slisketch::kQuantiles; ++j) q.append(slisketch::quantile_permille(j));
+    m.attr("SLISKETCH_EDGES") = py::tuple(edges);
+    m.attr("SLISKETCH_PERMILLE") = py::tuple(q);
+  }
+  py::class_<PySliSketch>(m, "SliSketch")
+      .def(py::init<int, int, int, int, int>(), py::arg("device") = 0, py::arg("span_cap") = 16384,
+           py::arg("group_cap") = 64, py::arg("windows") = 150, py::arg("n_buffers") = 3)
+      .def("step", &PySliSketch::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PySliSketch::query)
+      .def("results", &PySliSketch::results)
+      .def("step_ms", &PySliSketch::step_ms)
+      .def("rolling", &PySliSketch::rolling)
+      .def("window_hist", &PySliSketch::window_hist)
+      .def("sync", &PySliSketch::sync)
+      .def("close", &PySliSketch::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -96,7 +96,7 @@ class WindowPipeline:
                  halo_ms: float = 0.0, import_cap: int = 0, xchg_cap: int = 0, shard: Tuple[int, int] = (0, 1),
                  engine: str = "gpu", group=None, model_image: Optional[np.ndarray] = None, halo_windows: int = 3,
                  split_rings: bool = False, open_requests: int = 0, open_ttl_ms: float = 120000.0,
-                 open_reorder_ms: Optional[float] = None):
+                 open_reorder_ms: Optional[float] = None, sli_sketch: int = 0):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -110,7 +110,12 @@ class WindowPipeline:
         host oracle for "cpu"); ``results()`` then returns corrected ``sli`` / ``late``. 0: off.
         ``open_ttl_ms``: a counted request that never reports leaves the table after this long;
         ``open_reorder_ms`` (default 2 x ``window_ms``): how long an SLI record that came ahead of
-        its start record is remembered. One GPU only (no communicator, no sharding)."""
+        its start record is remembered. One GPU only (no communicator, no sharding).
+        ``sli_sketch`` > 0: keep per-service TTFT distributions of every window and of a rolling
+        horizon of that many windows (pipeline/slisketch.py; the device sketch for "gpu", the host
+        oracle for "cpu"); ``results()`` then also carries ``ttft_n`` / ``ttft_sum_ms`` / ``ttft_le`` /
+        ``ttft_q`` / ``ttft_q_roll`` / ``ttft_n_roll``. 0: off, nothing is constructed. Independent of
+        ``open_requests``; one GPU only as well."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -182,6 +187,22 @@ class WindowPipeline:
                 from .openreq import OpenRequestOracle
 
                 self.tracker = OpenRequestOracle(**tkw)
+        self.sketch = None
+        self._sli: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, sketch step)
+        if sli_sketch:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the TTFT sketch runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            skw = dict(span_cap=span_cap, group_cap=group_cap, windows=int(sli_sketch), n_buffers=self.nb,
+                       device=device)
+            if engine == "gpu":
+                from ..ops.slisketch import SliSketch
+
+                self.sketch = SliSketch(**skw)
+            else:
+                from .slisketch import SliSketchOracle
+
+                self.sketch = SliSketchOracle(**skw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -256,11 +277,16 @@ class WindowPipeline:
     def results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
         self.eng.wait(k)
         res = self.eng.results(k, n_groups)
-        if self.tracker is None:
-            return res
-        from .openreq import correct_results
+        if self.tracker is not None:
+            from .openreq import correct_results
 
-        return correct_results(res, self.open_results(k, n_groups))
+            res = correct_results(res, self.open_results(k, n_groups))
+        if self.sketch is not None:
+            from .slisketch import result_keys
+
+            res = dict(res)
+            res.update(result_keys(self.sli_results(k, n_groups)))
+        return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
     def track_open(self, spans, cut_ns: int, prev_cut_ns: int, n_groups: int) -> None:
@@ -285,9 +311,29 @@ class WindowPipeline:
         return {"dl": np.zeros((n_groups, 2), np.uint32), "dup": np.zeros((n_groups, 3), np.uint32),
                 "stats": np.zeros(N_STATS, np.uint32)}
 
+    # ---- TTFT distributions (pipeline/slisketch.py) -----------------------------------------
+    def track_sli(self, spans, n_groups: int) -> None:
+        """The sketch's step for the window about to be submitted: the same span ranges. Every
+        window steps, with or without a cut time (the horizon is counted in windows)."""
+        if self.sketch is None:
+            return
+        self._sli[self.k % self.nb] = (self.k, self.sketch.step(list(spans), int(n_groups)))
+
+    def sli_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The sketch's results of window k (pipeline/slisketch.py RESULT_FIELDS; an empty step's for
+        a window that was submitted past ``track_sli``)."""
+        held = self._sli.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.sketch.results(held[1], n_groups)
+        from .slisketch import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.sketch is not None:
+            self.sketch.close()
         self.eng.close()
 
     def results_all(self, k: int, n_groups: int) -> List[Dict[str, np.ndarray]]:
@@ -326,6 +372,8 @@ class WindowPipeline:
         self.eng.sync()
         if self.tracker is not None:
             self.tracker.sync()
+        if self.sketch is not None:
+            self.sketch.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -626,6 +674,8 @@ class RingWindowSource:
             pipe.track_open(spans, cut.t_ns, self.prev_cut_ns, n_groups)
             if int(cut.t_ns) > 0:
                 self.prev_cut_ns = int(cut.t_ns)
+        if pipe.sketch is not None:  # the TTFT distributions see the window's spans
+            pipe.track_sli(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
