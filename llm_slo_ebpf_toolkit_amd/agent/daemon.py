@@ -216,6 +216,10 @@ class AgentOptions:
     # (pipeline/slisketch.py); one GPU; nothing is checkpointed
     ttft_distribution: bool = False
     ttft_horizon_windows: int = 0        # windows of the rolling horizon (0: 5 minutes of windows)
+    # per service, the requests with the largest TTFT of the window and of the last windows, chosen on the
+    # GPU (pipeline/exemplars.py): ids on incidents and in the decision log; one GPU; nothing is checkpointed
+    request_exemplars: int = 0           # exemplars per service (1..8; 0: off)
+    exemplar_windows: int = 3            # windows the recent exemplars look back over (burn.current's span)
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -324,6 +328,7 @@ class Agent:
         self.burn = BurnRateForecaster(opts.slo_target, horizon=max(1, int(round(300_000 / max(opts.window_ms, 1)))),
                                        short=max(1, int(round(30_000 / max(opts.window_ms, 1)))))
         self.receiver = None
+        self.mapper = None  # the OTLP span mapper (its trace-id memory serves the request exemplars)
         self.attributions_emitted = 0
         # cut -> emission time of every window (ms): the agent's own share of detection delay
         self.emit_lag_ms: "collections.deque" = collections.deque(maxlen=4096)
@@ -734,6 +739,8 @@ class Agent:
                        and g < len(res["deadline"]) else {}),
                     **({"ttft_ms": self._ttft_row(res, g)} if res.get("ttft_n") is not None
                        and g < len(res["ttft_n"]) else {}),
+                    **({"exemplars": self._exemplar_rows(res, g)} if res.get("ex_recent") is not None
+                       and g < len(res["ex_recent"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -758,8 +765,38 @@ class Agent:
                 predicted_fault_domain=top.domain, confidence=float(top.posterior), evidence=ev,
                 slo_impact=SLOImpact("ttft_ms", round(burn, 4), impact_min),
                 fault_hypotheses=[FaultHypothesis(p.domain, p.posterior, p.evidence) for p in ranked
-                                  if p.posterior >= 0.01]))
+                                  if p.posterior >= 0.01],
+                **self._exemplar_ids(res, g)))
         return out
+
+    def _trace_id(self, trace_h: int) -> str:
+        """The W3C trace id of a record: 32 hex digits when the span mapper remembers the id's high
+        half, else the low 16 (``trace_h``)."""
+        hi = self.mapper.trace_high(trace_h) if self.mapper is not None else None
+        return f"{trace_h:016x}" if hi is None else f"{hi:016x}{trace_h:016x}"
+
+    def _exemplar_rows(self, res: dict, g: int) -> List[dict]:
+        """Group g's recent exemplars for the decision log, worst first."""
+        def ms(v):
+            v = float(v)
+            return round(v, 3) if math.isfinite(v) else None
+
+        rows = res["ex_recent"][g][:int(res["ex_k_recent"][g])]
+        return [{"trace_id": self._trace_id(int(r["trace_h"])), "span_id": f"{int(r['span_h']):016x}",
+                 "ttft_ms": ms(r["ttft_ms"]), "latency_ms": ms(r["latency_ms"]), "retrieval_ms": ms(r["retr_ms"]),
+                 "pod_id": int(r["pod_id"]), "pid": int(r["pid"]), "age": int(r["age"])} for r in rows]
+
+    def _exemplar_ids(self, res: dict, g: int) -> dict:
+        """``request_ids`` (span ids) and ``trace_ids`` (de-duplicated, order kept) of group g's recent
+        exemplars beyond the TTFT SLO; nothing when none is, or the tracker is off."""
+        if res.get("ex_recent") is None or g >= len(res["ex_recent"]):
+            return {}
+        rows = res["ex_recent"][g][:int(res["ex_k_recent"][g])]
+        rows = rows[rows["ttft_ms"] > np.float32(self.o.ttft_slo_ms)]
+        if not len(rows):
+            return {}
+        traces = list(dict.fromkeys(self._trace_id(int(t)) for t in rows["trace_h"]))
+        return {"request_ids": [f"{int(s):016x}" for s in rows["span_h"]], "trace_ids": traces}
 
     @staticmethod
     def _ttft_row(res: dict, g: int) -> dict:
@@ -817,6 +854,8 @@ class Agent:
             self.metrics.observe_open_requests(res["deadline"], head["open_requests"], names)
         if head.get("ttft_sketch") is not None and res.get("ttft_n") is not None:
             self.metrics.observe_ttft(res, head["ttft_sketch"], names)
+        if head.get("exemplars") is not None and res.get("ex_n") is not None:
+            self.metrics.observe_exemplars(res, head["exemplars"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -928,6 +967,9 @@ class Agent:
         if o.ttft_distribution and N > 1:
             raise ValueError("--ttft-distribution runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the TTFT sketch's are read on the host")
+        if o.request_exemplars and N > 1:
+            raise ValueError("--request-exemplars runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the exemplar tracker's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -973,7 +1015,8 @@ class Agent:
                             app_image=app_model_bytes(model).tobytes() if model.app is not None else b"",
                             open_requests=int(o.open_requests_cap) if o.deadline_breach else 0,
                             open_reorder_ms=2.0 * float(o.window_ms),
-                            sli_sketch=self.ttft_horizon() if o.ttft_distribution else 0)
+                            sli_sketch=self.ttft_horizon() if o.ttft_distribution else 0,
+                            exemplars=int(o.request_exemplars), exemplar_windows=int(o.exemplar_windows))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):
@@ -1011,6 +1054,8 @@ class Agent:
                     return ipcache["m"]
             mapper = SpanMapper(groups, self.pod_ids.id, node_id, pod_ips=pod_ips, forwarders=o.otlp_forwarders)
             mapper.slo_ms = float(o.ttft_slo_ms)
+            mapper.keep_trace_high = bool(o.request_exemplars)  # exemplars quote the whole W3C trace id
+            self.mapper = mapper
             if router is not None:  # each span to the ring of the worker owning its incident group
                 def push_spans(recs):
                     sh = router.span_shard(recs)

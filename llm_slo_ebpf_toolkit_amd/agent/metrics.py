@@ -115,6 +115,15 @@ class AgentMetrics:
                                      "TTFT sketch events: invalid (a counted record with a NaN or negative TTFT, in "
                                      "no bucket), underflow (below 0.125 ms), overflow (2^21 ms or more).",
                                      ("reason",))
+        # request exemplars (agent --request-exemplars, pipeline/exemplars.py): the exact maximum, which
+        # the sketch's buckets cannot give. Plain series: no OpenMetrics exemplar syntax
+        self.ttft_max = r.gauge("llm_slo_agent_ttft_max_ms",
+                                "Largest TTFT (ms) of the last window by service: the first request exemplar, "
+                                "chosen on the GPU (exact).", ("service",))
+        self.exemplar_events = r.counter("llm_slo_agent_exemplar_events_total",
+                                         "Request-exemplar events: invalid (a counted record with a NaN or negative "
+                                         "TTFT), out_of_group (an SLI record of a group beyond the window's).",
+                                         ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -251,6 +260,18 @@ class AgentMetrics:
                         self.ttft_quantile.set(v, svc, name, scope)
         for reason in EVENT_STATS:
             self.ttft_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_exemplars(self, res: dict, stats: dict, names) -> None:
+        """One window of the exemplar tracker: ``res`` carries ex_k_win / ex_win per group
+        (pipeline/exemplars.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.exemplars import EVENT_STATS
+
+        for g, have in enumerate(np.asarray(res["ex_k_win"]).tolist()):
+            if have:  # a window without a record keeps the last value: NaN would break max()
+                v = float(res["ex_win"][g][0]["ttft_ms"])
+                self.ttft_max.set(v, names[g] if g < len(names) else f"group-{g}")
+        for reason in EVENT_STATS:
+            self.exemplar_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

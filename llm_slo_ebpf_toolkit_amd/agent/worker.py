@@ -82,6 +82,8 @@ class WorkerSpec:
     open_requests: int = 0      # entries of the open-request table (agent --deadline-breach); 0: off
     open_reorder_ms: float = 2000.0
     sli_sketch: int = 0         # windows of the TTFT sketch's rolling horizon (agent --ttft-distribution); 0: off
+    exemplars: int = 0          # worst-TTFT exemplars per service (agent --request-exemplars); 0: off
+    exemplar_windows: int = 3   # windows of their horizon (agent --exemplar-windows)
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -95,7 +97,8 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     world = len(parts)
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
-                "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll"):
+                "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
+                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -164,7 +167,8 @@ class WorkerCore:
                                    xchg_cap=spec.xchg_cap, shard=(spec.rank, spec.world), engine=spec.engine,
                                    group=group, model_image=np.frombuffer(spec.model_image, dtype=np.uint8),
                                    split_rings=spec.split, open_requests=spec.open_requests,
-                                   open_reorder_ms=spec.open_reorder_ms, sli_sketch=spec.sli_sketch)
+                                   open_reorder_ms=spec.open_reorder_ms, sli_sketch=spec.sli_sketch,
+                                   exemplars=spec.exemplars, exemplar_windows=spec.exemplar_windows)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -288,6 +292,10 @@ class WorkerCore:
                 from ..pipeline.slisketch import stats_dict as sketch_stats
 
                 d["ttft_sketch"] = sketch_stats(pipe.sli_results(k, n_groups)["stats"])
+            if pipe.exemplars is not None:  # the exemplar tracker's statistics of the window
+                from ..pipeline.exemplars import stats_dict as exemplar_stats
+
+                d["exemplars"] = exemplar_stats(pipe.exemplar_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

@@ -119,6 +119,13 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                      "horizon is not checkpointed"),
         ("ttft-horizon-windows", d.ttft_horizon_windows, "--ttft-distribution: windows of the rolling horizon "
                                                          "(0 = round(300000 / window-ms): 5 minutes)"),
+        ("request-exemplars", d.request_exemplars, "gpu engine: per service, this many requests with the largest "
+                                                   "TTFT of the window and of the last windows, chosen on the GPU "
+                                                   "-- trace_ids / request_ids on incidents, an exemplars field in "
+                                                   "the decision log, llm_slo_agent_ttft_max_ms{service} (1..8; 0 = "
+                                                   "off); one GPU only; the horizon is not checkpointed"),
+        ("exemplar-windows", d.exemplar_windows, "--request-exemplars: windows the recent exemplars look back over "
+                                                 "(1..16; 3 = the span of the emission gate's burn)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -169,6 +176,7 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         decision_log=a.decision_log, deadline_breach=bool(a.deadline_breach),
         open_requests_cap=int(a.open_requests_cap),
         ttft_distribution=bool(a.ttft_distribution), ttft_horizon_windows=int(a.ttft_horizon_windows),
+        request_exemplars=int(a.request_exemplars), exemplar_windows=int(a.exemplar_windows),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -84,6 +84,18 @@ def trace_hash(trace_id) -> int:
     return h or 1
 
 
+def trace_high_half(trace_id) -> Optional[int]:
+    """High 64 bits of a 128-bit W3C trace id (hex string or 16 bytes); None for a shorter id."""
+    try:
+        if isinstance(trace_id, (bytes, bytearray)):
+            b = bytes(trace_id)
+            return int.from_bytes(b[-16:-8], "big") if len(b) >= 16 else None
+        s = str(trace_id or "").strip().lower()
+        return int(s[-32:-16], 16) if len(s) >= 32 else None
+    except ValueError:
+        return None
+
+
 def span_hash(span_id) -> int:
     if not span_id:
         return 0
@@ -325,6 +337,16 @@ class SpanMapper:
         self._early: "collections.OrderedDict[int, bool]" = collections.OrderedDict()
         self._final: "collections.OrderedDict[int, bool]" = collections.OrderedDict()
         self.early_dropped = 0  # first-token records after their request span (counted by it)
+        # request exemplars (agent --request-exemplars): ``trace_h`` is the low 64 bits of the W3C id;
+        # with this set the high half of every record's id is remembered, bounded, oldest out. Off:
+        # nothing is kept
+        self.keep_trace_high = False
+        self._high: "collections.OrderedDict[int, int]" = collections.OrderedDict()
+
+    def trace_high(self, trace_h: int) -> Optional[int]:
+        """The high 64 bits of the W3C trace id whose low half is ``trace_h``, while remembered."""
+        with self._rlock:
+            return self._high.get(int(trace_h))
 
     def take_pod_updates(self) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         """(pod ids, svc|node) learned since the last call, or None."""
@@ -419,6 +441,14 @@ class SpanMapper:
             dport = _first(a, ("server.port", "net.peer.port", "net.sock.peer.port")) or 0
             v = _first(a, TTFT_KEYS)
             th = trace_hash(d.get("traceId"))
+            if self.keep_trace_high and th:
+                hi = trace_high_half(d.get("traceId"))
+                if hi is not None:
+                    with self._rlock:
+                        self._high[th] = hi
+                        self._high.move_to_end(th)
+                        while len(self._high) > self.retrieval_cap:
+                            self._high.popitem(last=False)
             fl = 0
             # a start record (llm.slo.request_start, no TTFT yet): joins, never counts, and leaves
             # the first-token / request-span pairing and the trace's retrieval breakdown alone

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "engine.h"
+#include "exemplars.h"
 #include "openreq.h"
 #include "slisketch.h"
 
@@ -460,6 +461,87 @@ class PySliSketch {
   std::unique_ptr<SliSketch> t_;
 };
 
+// The request-exemplar tracker (exemplars.h): one step per window over the same span ranges the
+// engine gets; results per step index. Rows leave as bytes [.., 64] (pipeline/exemplars.py EXEMPLAR).
+class PyExemplarTracker {
+ public:
+  PyExemplarTracker(int device, int k, int windows, int64_t span_cap, int group_cap, int n_buffers, bool lds) {
+    if (span_cap < 1 || span_cap >= (int64_t(1) << 31))
+      throw std::invalid_argument("request exemplars: span_cap must be in [1, 2^31)");
+    exemplars::Config c;
+    c.device = device;
+    c.k = k;
+    c.windows = windows;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.lds = lds;
+    exemplars::validate(c);
+    t_ = std::make_unique<ExemplarTracker>(c);
+  }
+  ExemplarTracker& t() {
+    if (!t_) throw std::logic_error("request exemplars closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    ExemplarTracker& ex = t();
+    py::gil_scoped_release nogil;
+    return ex.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    ExemplarTracker& ex = t();
+    if (n_groups < 0 || n_groups > ex.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = ex.results(i);
+    }
+    const exemplars::Layout& l = ex.result_layout();
+    const py::ssize_t G = n_groups, K = ex.config().k;
+    py::dict d;
+    d["n"] = copy_array(r + l.n, {G});
+    d["k_win"] = copy_array(r + l.k_win, {G});
+    d["k_recent"] = copy_array(r + l.k_recent, {G});
+    d["win"] = copy_array(reinterpret_cast<const uint8_t*>(r + l.win), {G, K, exemplars::kRowBytes});
+    d["recent"] = copy_array(reinterpret_cast<const uint8_t*>(r + l.recent), {G, K, exemplars::kRowBytes});
+    d["stats"] = copy_array(r + l.stats, {exemplars::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  py::tuple resident() {
+    ExemplarTracker& ex = t();
+    std::pair<std::vector<exemplars::Row>, std::vector<uint32_t>> h;
+    {
+      py::gil_scoped_release nogil;
+      h = ex.resident();
+    }
+    const py::ssize_t H = ex.config().windows, G = ex.config().group_cap, K = ex.config().k;
+    return py::make_tuple(copy_array(reinterpret_cast<const uint8_t*>(h.first.data()), {H, G, K, exemplars::kRowBytes}),
+                          copy_array(h.second.data(), {H, G}));
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<ExemplarTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -525,6 +607,22 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("window_hist", &PySliSketch::window_hist)
       .def("sync", &PySliSketch::sync)
       .def("close", &PySliSketch::close);
+  m.attr("EXEMPLAR_MAX_K") = exemplars::kMaxK;
+  m.attr("EXEMPLAR_MAX_H") = exemplars::kMaxH;
+  m.attr("EXEMPLAR_LDS_GROUPS") = exemplars::kLdsGroups;
+  m.attr("EXEMPLAR_ROW_BYTES") = exemplars::kRowBytes;
+  m.attr("EXEMPLAR_STATS") = (int)exemplars::kStats;
+  py::class_<PyExemplarTracker>(m, "ExemplarTracker")
+      .def(py::init<int, int, int, int64_t, int, int, bool>(), py::arg("device") = 0, py::arg("k") = 3,
+           py::arg("windows") = 3, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("n_buffers") = 3,
+           py::arg("lds") = true)
+      .def("step", &PyExemplarTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyExemplarTracker::query)
+      .def("results", &PyExemplarTracker::results)
+      .def("step_ms", &PyExemplarTracker::step_ms)
+      .def("resident", &PyExemplarTracker::resident)
+      .def("sync", &PyExemplarTracker::sync)
+      .def("close", &PyExemplarTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -96,7 +96,8 @@ class WindowPipeline:
                  halo_ms: float = 0.0, import_cap: int = 0, xchg_cap: int = 0, shard: Tuple[int, int] = (0, 1),
                  engine: str = "gpu", group=None, model_image: Optional[np.ndarray] = None, halo_windows: int = 3,
                  split_rings: bool = False, open_requests: int = 0, open_ttl_ms: float = 120000.0,
-                 open_reorder_ms: Optional[float] = None, sli_sketch: int = 0):
+                 open_reorder_ms: Optional[float] = None, sli_sketch: int = 0, exemplars: int = 0,
+                 exemplar_windows: int = 3):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -115,7 +116,11 @@ class WindowPipeline:
         horizon of that many windows (pipeline/slisketch.py; the device sketch for "gpu", the host
         oracle for "cpu"); ``results()`` then also carries ``ttft_n`` / ``ttft_sum_ms`` / ``ttft_le`` /
         ``ttft_q`` / ``ttft_q_roll`` / ``ttft_n_roll``. 0: off, nothing is constructed. Independent of
-        ``open_requests``; one GPU only as well."""
+        ``open_requests``; one GPU only as well.
+        ``exemplars`` > 0: keep, per service, that many records with the largest TTFT of every window
+        and of the last ``exemplar_windows`` windows (pipeline/exemplars.py; the device tracker for
+        "gpu", the host oracle for "cpu"); ``results()`` then also carries ``ex_n`` / ``ex_k_win`` /
+        ``ex_win`` / ``ex_k_recent`` / ``ex_recent``. 0: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -203,6 +208,22 @@ class WindowPipeline:
                 from .slisketch import SliSketchOracle
 
                 self.sketch = SliSketchOracle(**skw)
+        self.exemplars = None
+        self._ex: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if exemplars:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("request exemplars run on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            ekw = dict(k=int(exemplars), windows=int(exemplar_windows), span_cap=span_cap, group_cap=group_cap,
+                       n_buffers=self.nb, device=device)
+            if engine == "gpu":
+                from ..ops.exemplars import ExemplarTracker
+
+                self.exemplars = ExemplarTracker(**ekw)
+            else:
+                from .exemplars import ExemplarOracle
+
+                self.exemplars = ExemplarOracle(**ekw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -286,6 +307,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(result_keys(self.sli_results(k, n_groups)))
+        if self.exemplars is not None:
+            from .exemplars import result_keys as exemplar_keys
+
+            res = dict(res)
+            res.update(exemplar_keys(self.exemplar_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -329,9 +355,29 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- request exemplars (pipeline/exemplars.py) ------------------------------------------
+    def track_exemplars(self, spans, n_groups: int) -> None:
+        """The exemplar tracker's step for the window about to be submitted: the same span ranges.
+        Every window steps (the horizon is counted in windows)."""
+        if self.exemplars is None:
+            return
+        self._ex[self.k % self.nb] = (self.k, self.exemplars.step(list(spans), int(n_groups)))
+
+    def exemplar_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The exemplar tracker's results of window k (pipeline/exemplars.py RESULT_FIELDS; an empty
+        step's for a window that was submitted past ``track_exemplars``)."""
+        held = self._ex.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.exemplars.results(held[1], n_groups)
+        from .exemplars import empty_result
+
+        return empty_result(n_groups, self.exemplars.k)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.exemplars is not None:
+            self.exemplars.close()
         if self.sketch is not None:
             self.sketch.close()
         self.eng.close()
@@ -374,6 +420,8 @@ class WindowPipeline:
             self.tracker.sync()
         if self.sketch is not None:
             self.sketch.sync()
+        if self.exemplars is not None:
+            self.exemplars.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -676,6 +724,8 @@ class RingWindowSource:
                 self.prev_cut_ns = int(cut.t_ns)
         if pipe.sketch is not None:  # the TTFT distributions see the window's spans
             pipe.track_sli(spans, n_groups)
+        if pipe.exemplars is not None:  # and so do the request exemplars
+            pipe.track_exemplars(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
