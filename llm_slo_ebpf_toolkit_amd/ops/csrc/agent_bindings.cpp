@@ -671,6 +671,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("sent_block", &PyEngine::sent_block)
       .def("close", &PyEngine::close)
       .def_property_readonly("buffers", &PyEngine::buffers)
+      .def_property_readonly("copy_lanes", [](PyEngine& p) { return p.eng().copy_lanes(); })
       .def_property_readonly("windows_folded", &PyEngine::folded)
       .def_property_readonly("graphs", &PyEngine::graphs)
       .def_property_readonly("host_issue_us", &PyEngine::host_issue_us)

@@ -5,7 +5,9 @@
 //                    host never reads or rewrites a record
 //   copy stream    : DMA of the window's ring bytes straight from the (registered) rings into
 //                    device block b: the BPF ring's framed records as the kernel wrote them,
-//                    the user-space producers' 64-byte records, the spans, the counts
+//                    the user-space producers' 64-byte records, the spans. With overlapped
+//                    windows there can be two of them (copy lanes, below at copy_): window k's
+//                    DMAs then go to lane k & 1
 //   compute stream : [device refit from window k - nb's all-reduced statistics]
 //                    graph(b): reset accumulators -> ring definitions (context rows, trace
 //                    map) -> K1 decode (framed + user records) -> partition -> spans -> K2 LDS
@@ -43,6 +45,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "copylanes.h"
 #include "mislo_launch.h"
 #include "mislo_packet.h"
 
@@ -153,8 +156,11 @@ class WindowEngine {
   // Queue window k (in order). Returns when its DMAs and kernels are queued; the ring bytes
   // must stay untouched until h2d_done(k).
   void submit(int64_t k, const WindowInput& in, bool with_labels, bool learn);
-  bool h2d_done(int64_t k);   // window k's input DMAs completed (its ring space may be freed)
+  // the input DMAs of every window up to k completed (their ring space may be freed): never true
+  // for a window while an earlier one is still being read, whichever lane finishes first
+  bool h2d_done(int64_t k);
   void wait_h2d(int64_t k);
+  int copy_lanes() const { return lanes_; }
   bool query(int64_t k);      // window k's results are in host memory
   void wait(int64_t k);
   const double* packet(int64_t k) const { return bufs_[k % nb_].packet_host; }
@@ -162,7 +168,10 @@ class WindowEngine {
   ResultLayout layout() const { return ResultLayout{(size_t)cfg_.group_cap}; }
   // device time of window k (ms): DMA start -> results in host memory, and the compute stream's share
   std::pair<float, float> window_ms(int64_t k);
-  std::vector<float> copy_ms(int64_t k);  // window k's DMA time and the copy stream's idle gap before it
+  // window k's DMA span (first DMA's start to the last one's end: with two lanes it shares the
+  // link with its neighbours' DMAs) and the time from window k - 1's last DMA to window k's first
+  // (negative when they overlap)
+  std::vector<float> copy_ms(int64_t k);
 
   void set_model_bytes(const void* bytes, size_t n);  // stream-ordered before the next window
   // device refit parameters (smoothing, prior pseudo-count, 1 / temperature, minimum labelled mass
@@ -314,7 +323,8 @@ class WindowEngine {
   // (slots_ = gens_ + 1): docs/ARCHITECTURE.md, "Window overlap". On where the span branch would
   // be (not with MISLO_ONE_STREAM), never with the exchange or a communicator;
   // MISLO_WINDOW_OVERLAP=0/1 overrides. The span branch is then off unless MISLO_SPAN_STREAM=1:
-  // three streams (copy, front, compute) and branch-free graphs keep one hardware queue each.
+  // copy, front and compute with branch-free graphs keep one hardware queue each (the second
+  // copy lane draws its queue from the other priority's pool, at copy_).
   hipStream_t front_ = nullptr;
   bool overlap_ = false;
   // The state both stages of a window touch, one set per buffer with overlapped windows (else
@@ -346,8 +356,9 @@ class WindowEngine {
     uint32_t* remote_n;                   // their count
     const BufSet* set;
     const GenMeta* gen_prev;  // the previous window's: buffer b - 1's set (or this one's own)
-    hipEvent_t h2d_done, h2d_part, head_done, front_done, compute_done, comm_done, xchg_done;
-    hipEvent_t t_start, t_copy_end, t_comp0, t_comp1, t_end;
+    // h2d_done: the window's last DMA ended (timed: it is also the end of the window's copy span)
+    hipEvent_t h2d_done, head_done, front_done, compute_done, comm_done, xchg_done;
+    hipEvent_t t_start, t_comp0, t_comp1, t_end;
     const int* counts() const { return reinterpret_cast<const int*>(in); }
   };
   std::vector<Buf> bufs_;
@@ -357,7 +368,19 @@ class WindowEngine {
   bool exchange() const { return comm_ && cfg_.xchg_cap > 0 && cfg_.import_cap > 0; }
   JoinParams jp_{};
   int nblk_sig_ = 1, nblk_span_ = 1;
-  hipStream_t copy_ = nullptr, copy2_ = nullptr, compute_ = nullptr, comm_stream_ = nullptr;
+  // Copy lanes (copylanes.h): window k's three DMAs go back to back to copy_[k & 1] when there
+  // are two, so one lane's DMAs are already queued on its engine while the other hands a finished
+  // window over to its end marker and the next window's start marker. Two with overlapped windows
+  // and four or more buffers (MISLO_COPY_LANES=1|2 overrides where windows overlap; with three
+  // buffers two lanes did not beat one, alloc()); one with MISLO_ONE_STREAM, with the exchange
+  // sized in, and from init_comm on. The second lane is created at the highest stream priority, which draws its
+  // hardware queue from the other pool than copy, front and compute (MISLO_COPY_LANE_PRIO=0:
+  // default priority).
+  hipStream_t copy_[kMaxCopyLanes] = {nullptr, nullptr};
+  int lanes_ = 1;
+  CopiedUpTo copied_;
+  bool copied_ready(int64_t w, bool block);
+  hipStream_t compute_ = nullptr, comm_stream_ = nullptr;
   ncclComm_t comm_ = nullptr;
   ncclComm_t xcomm_ = nullptr;  // the trace-row exchange's communicator (compute stream; init_comm)
   // device buffers shared by every window

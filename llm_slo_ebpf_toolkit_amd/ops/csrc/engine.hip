@@ -78,7 +78,6 @@ void to_host(const void* src, void* dst, size_t bytes, hipStream_t st) {
 }
 
 constexpr unsigned kEvWait = hipEventDisableTiming | hipEventBlockingSync;  // events the host sleeps on
-
 // an integer environment knob, `unset` where it is not set
 int env_int(const char* name, int unset) {
   const char* v = getenv(name);
@@ -205,16 +204,23 @@ void WindowEngine::alloc() {
   // (tools/rss_probe.py); the bench keeps the two streams (copy / compute overlap on 4 queues).
   const bool one_stream = env_int("MISLO_ONE_STREAM", 0) == 1;
   compute_ = mk_stream();
-  copy_ = one_stream ? compute_ : mk_stream();
+  copy_[0] = one_stream ? compute_ : mk_stream();
   spin_ = env_int("MISLO_SPIN_WAIT", 0) == 1;  // wait() polls its event instead of sleeping on it
-  // MISLO_COPY_STREAMS=2 splits a window's DMA over two streams (measured slower: the second
-  // stream's large copy blocks the issuing thread ~0.2 ms per window)
-  copy2_ = env_int("MISLO_COPY_STREAMS", 0) == 2 && !one_stream ? mk_stream() : copy_;
   // Window overlap (engine.h): the front stage on a stream of its own. Not for an engine sized
   // for the exchange (its windows run the two-part serial chain), and switched off by init_comm.
   overlap_ = env_int("MISLO_WINDOW_OVERLAP", !one_stream) == 1 && !one_stream &&
              !(cfg_.xchg_cap > 0 && cfg_.import_cap > 0);
   if (overlap_) front_ = mk_stream();
+  // Copy lanes (engine.h, copylanes.h): a second copy stream, windows alternating, where windows
+  // overlap. A window's own DMAs stay on one stream (one window split over the two streams
+  // measured slower). Two lanes by default from four buffers on only: with three, window k's
+  // DMAs are issued once window k - 3's results are in, the lanes seldom hold a backlog, and
+  // when they do each window's copy takes longer beside its neighbour's than the three-window
+  // pipeline hides -- 0.421-0.432 ms per window with two lanes against 0.418-0.443 with one, one
+  // lane ahead in two sessions of three; with four buffers 0.399-0.403 against 0.423-0.431
+  // (profiles/copy_lanes/README.md).
+  lanes_ = overlap_ && env_int("MISLO_COPY_LANES", nb_ >= 4 ? 2 : 1) == 2 ? 2 : 1;
+  copy_[1] = lanes_ == 2 ? mk_stream(env_int("MISLO_COPY_LANE_PRIO", 1) != 0) : copy_[0];
   slots_ = gens_ + (overlap_ ? 1 : 0);
   {
     // The span side of the chain (decode, partition, sort, the probe's work list) on a second
@@ -249,10 +255,10 @@ void WindowEngine::alloc() {
     buf.head_host = static_cast<uint8_t*>(host_block(head));
     buf.packet_dev = dalloc<double>(kPacketLen, true);
     buf.packet_host = static_cast<double*>(host_block(kPacketLen * sizeof(double)));
-    for (hipEvent_t* e : {&buf.h2d_done, &buf.h2d_part, &buf.head_done, &buf.compute_done, &buf.comm_done,
-                          &buf.front_done, &buf.xchg_done})
+    for (hipEvent_t* e : {&buf.head_done, &buf.compute_done, &buf.comm_done, &buf.front_done, &buf.xchg_done})
       *e = mk_event(kEvWait);
-    for (hipEvent_t* e : {&buf.t_start, &buf.t_copy_end, &buf.t_comp0, &buf.t_comp1, &buf.t_end})
+    buf.h2d_done = mk_event(hipEventBlockingSync);  // the host sleeps on it, and it ends the copy's timed span
+    for (hipEvent_t* e : {&buf.t_start, &buf.t_comp0, &buf.t_comp1, &buf.t_end})
       *e = mk_event(hipEventDefault);  // timing
     buf.res_host = static_cast<uint8_t*>(host_block(lay.bytes()));
     buf.res_dev = dalloc<uint8_t>(lay.bytes(), true);
@@ -412,18 +418,28 @@ size_t WindowEngine::dma(const std::vector<Seg>& segs, uint8_t* dst, size_t cap,
   return off;
 }
 
-bool WindowEngine::h2d_done(int64_t k) {
-  for (hipEvent_t ev : {bufs_[k % nb_].h2d_done, bufs_[k % nb_].h2d_part}) {  // both copy streams
-    const hipError_t e = hipEventQuery(ev);
-    if (e == hipErrorNotReady) return false;
-    HIPCHECK(e);
+// Window w's completion event, for a window copied_ does not know copied yet: its buffer's event
+// is still its own (CopiedUpTo, copylanes.h).
+bool WindowEngine::copied_ready(int64_t w, bool block) {
+  const hipEvent_t ev = bufs_[w % nb_].h2d_done;
+  if (block) {
+    HIPCHECK(hipEventSynchronize(ev));
+    return true;
   }
+  const hipError_t e = hipEventQuery(ev);
+  if (e == hipErrorNotReady) return false;
+  HIPCHECK(e);
   return true;
 }
 
+bool WindowEngine::h2d_done(int64_t k) {
+  if (k < 0 || k >= submitted_) return false;  // not queued: nothing of it has been copied
+  return copied_.done(k, lanes_, [this](int64_t w) { return copied_ready(w, false); });
+}
+
 void WindowEngine::wait_h2d(int64_t k) {
-  HIPCHECK(hipEventSynchronize(bufs_[k % nb_].h2d_done));
-  HIPCHECK(hipEventSynchronize(bufs_[k % nb_].h2d_part));
+  if (k < 0 || k >= submitted_) throw std::invalid_argument("wait_h2d: the window has not been submitted");
+  copied_.done(k, lanes_, [this](int64_t w) { return copied_ready(w, true); });
 }
 
 // The head of a window: the accumulators reset, the next generation slot, the window's rows.
@@ -646,10 +662,11 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   // host back-pressure: at most max_ahead windows queued beyond the one computing
   Lap phase;
   if (k >= max_ahead_) HIPCHECK(hipEventSynchronize(bufs_[(k - max_ahead_) % nb_].compute_done));
-  // the pinned head / staging of the buffer were last read by the DMAs of window k - nb
+  // the pinned head / staging of the buffer were last read by the DMAs of window k - nb (on
+  // whichever lane they ran: the event is the buffer's), which also wrote the device block last
   if (k >= nb_) {
     HIPCHECK(hipEventSynchronize(buf.h2d_done));
-    HIPCHECK(hipEventSynchronize(buf.h2d_part));
+    copied_.reused(k, nb_);  // before the event is recorded again below
     HIPCHECK(hipEventSynchronize(buf.head_done));
   }
   phase(wait_us_);
@@ -669,30 +686,31 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   c[15] = (int32_t)n_k;
   int32_t* lab = reinterpret_cast<int32_t*>(buf.head_host + kHeadBytes);
   for (int g = 0; g < cfg_.group_cap; ++g) lab[g] = (in.labels && g < n_groups) ? in.labels[g] : -1;
-  // DMAs once window k - nb (the device block's previous reader) computed: the BPF ring's
-  // bytes, the user-space records and the spans, back to back on the copy stream (or over two
-  // streams with MISLO_COPY_STREAMS=2); the head is loaded on the compute stream (below).
-  HIPCHECK(hipStreamWaitEvent(copy_, buf.compute_done, 0));
-  HIPCHECK(hipStreamWaitEvent(copy2_, buf.compute_done, 0));
-  HIPCHECK(hipEventRecord(buf.t_start, copy_));
+  // The window's DMAs: the BPF ring's bytes, the user-space records and the spans, back to back
+  // on the window's copy lane between one start marker and one completion event; the head is
+  // loaded on the compute stream (below). The copy stream waits for nothing on the device: the
+  // device block's previous reader, window k - nb, has computed, because the host waited above
+  // for compute_done of window k - max_ahead_, max_ahead_ <= nb_ (constructor) and every stage
+  // that reads the block (front_, side_) is joined into the in-order compute stream before that
+  // event. A wait on the copy stream costs a queue hand-off with the link idle.
+  const hipStream_t cs = copy_[copy_lane(k, lanes_)];
+  HIPCHECK(hipEventRecord(buf.t_start, cs));
   size_t st_off = 0;
   Lap part;  // DMA issue: ring bytes, head (nothing: not on the copy stream), user records, spans
-  dma(in.kernel, buf.in + off_kern_, kern_bytes(), buf.staging, st_off, copy_);
+  dma(in.kernel, buf.in + off_kern_, kern_bytes(), buf.staging, st_off, cs);
   part(split_us_[0]);
   part(split_us_[1]);
-  dma(in.user, buf.in + off_user_, 64 * (size_t)cfg_.user_cap, buf.staging, st_off, copy2_);
+  dma(in.user, buf.in + off_user_, 64 * (size_t)cfg_.user_cap, buf.staging, st_off, cs);
   part(split_us_[2]);
-  dma(in.spans, buf.in + off_span_, 64 * (size_t)cfg_.span_cap, buf.staging, st_off, copy2_);
+  dma(in.spans, buf.in + off_span_, 64 * (size_t)cfg_.span_cap, buf.staging, st_off, cs);
   part(split_us_[3]);
-  HIPCHECK(hipEventRecord(buf.h2d_part, copy2_));
-  HIPCHECK(hipEventRecord(buf.h2d_done, copy_));
-  HIPCHECK(hipEventRecord(buf.t_copy_end, copy2_));
+  HIPCHECK(hipEventRecord(buf.h2d_done, cs));
   phase(dma_us_);
   // the stream of the window's head and front half: front_ with overlapped windows (never with
-  // the exchange: overlap_ is off for an engine sized for it or holding a communicator)
+  // the exchange: overlap_ is off for an engine sized for it or holding a communicator). It waits
+  // for this window's own DMAs only, whatever the other lane is doing.
   hipStream_t fs = overlap_ ? front_ : compute_;
   HIPCHECK(hipStreamWaitEvent(fs, buf.h2d_done, 0));
-  HIPCHECK(hipStreamWaitEvent(fs, buf.h2d_part, 0));
   // overlapped: the front stage of window k starts once the back stage of window k - 2 ended. It
   // overwrites the generation slot that stage probed as its oldest, and (two buffers) the buffer
   // set and the head that stage read; with it at most one window's back stage runs beside a front.
@@ -813,12 +831,15 @@ void WindowEngine::wait(int64_t k) {
 }
 
 std::vector<float> WindowEngine::copy_ms(int64_t k) {
-  // [copy duration of window k, copy-engine idle time between window k-1's DMAs and k's]
+  // [window k's DMA span, window k-1's last DMA's end to window k's first DMA's start]. One lane:
+  // the copy's duration and the copy stream's idle time before it. Two lanes: windows k-1 and k
+  // copy side by side and share the link, so the span is longer than the bytes alone would take
+  // and the second value is negative where they overlap.
   const Buf& buf = bufs_[k % nb_];
   float dur = 0.f, gap = -1.f;
-  HIPCHECK(hipEventSynchronize(buf.t_copy_end));
-  HIPCHECK(hipEventElapsedTime(&dur, buf.t_start, buf.t_copy_end));
-  if (k >= 1 && nb_ > 1) HIPCHECK(hipEventElapsedTime(&gap, bufs_[(k - 1) % nb_].t_copy_end, buf.t_start));
+  HIPCHECK(hipEventSynchronize(buf.h2d_done));
+  HIPCHECK(hipEventElapsedTime(&dur, buf.t_start, buf.h2d_done));
+  if (k >= 1 && nb_ > 1) HIPCHECK(hipEventElapsedTime(&gap, bufs_[(k - 1) % nb_].h2d_done, buf.t_start));
   return {dur, gap};
 }
 
@@ -970,6 +991,7 @@ void WindowEngine::init_comm(const ncclUniqueId& id, int rank, int world) {
   if (overlap_) {  // the windows of an engine with a communicator run the serial chain on compute_
     HIPCHECK(hipStreamSynchronize(front_));  // a pod table upload queued there
     overlap_ = false;
+    lanes_ = 1;  // no window has been submitted: lane 1 stays idle
     // the serial chain's default again: the span side on its own stream
     if (!getenv("MISLO_SPAN_STREAM")) enable_span_branch();
   }
@@ -1047,8 +1069,8 @@ void WindowEngine::model_bytes(void* out) {
 }
 
 void WindowEngine::sync() {
-  HIPCHECK(hipStreamSynchronize(copy_));
-  if (copy2_ != copy_) HIPCHECK(hipStreamSynchronize(copy2_));
+  HIPCHECK(hipStreamSynchronize(copy_[0]));
+  if (copy_[1] != copy_[0]) HIPCHECK(hipStreamSynchronize(copy_[1]));
   if (front_) HIPCHECK(hipStreamSynchronize(front_));  // the front stages (and a pod table upload)
   HIPCHECK(hipStreamSynchronize(compute_));
   HIPCHECK(hipStreamSynchronize(comm_stream_));
