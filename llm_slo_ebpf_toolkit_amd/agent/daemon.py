@@ -220,6 +220,12 @@ class AgentOptions:
     # GPU (pipeline/exemplars.py): ids on incidents and in the decision log; one GPU; nothing is checkpointed
     request_exemplars: int = 0           # exemplars per service (1..8; 0: off)
     exemplar_windows: int = 3            # windows the recent exemplars look back over (burn.current's span)
+    # per service, the pods seen, the pods breaching the TTFT SLO and the pods with the most breaches, of the
+    # window and of the last windows, ranked on the GPU (pipeline/podrank.py): a pods field in the decision
+    # log and three gauges; one GPU; nothing is checkpointed
+    pod_breakdown: int = 0               # ranked pods per service (1..8; 0: off)
+    pod_breakdown_windows: int = 3       # windows the recent scope looks back over (burn.current's span)
+    pod_pairs: int = 4096                # distinct (service, pod) pairs a window may hold
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -741,6 +747,8 @@ class Agent:
                        and g < len(res["ttft_n"]) else {}),
                     **({"exemplars": self._exemplar_rows(res, g)} if res.get("ex_recent") is not None
                        and g < len(res["ex_recent"]) else {}),
+                    **({"pods": self._pod_entry(res, g)} if res.get("pod_rec_top") is not None
+                       and g < len(res["pod_rec_top"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -785,6 +793,20 @@ class Agent:
         return [{"trace_id": self._trace_id(int(r["trace_h"])), "span_id": f"{int(r['span_h']):016x}",
                  "ttft_ms": ms(r["ttft_ms"]), "latency_ms": ms(r["latency_ms"]), "retrieval_ms": ms(r["retr_ms"]),
                  "pod_id": int(r["pod_id"]), "pid": int(r["pid"]), "age": int(r["age"])} for r in rows]
+
+    def _pod_entry(self, res: dict, g: int) -> dict:
+        """Group g's pod breakdown over the recent windows for the decision log, worst pod first."""
+        names = self.pod_ids.names()
+        breaches = int(res["pod_rec_b"][g])
+        top = []
+        for r in res["pod_rec_top"][g][:int(res["pod_rec_k_top"][g])]:
+            pod, n, b, mx = int(r["pod_id"]), int(r["n"]), int(r["b"]), float(r["max_ttft"])
+            top.append({"pod": (names[pod] or "") if pod < len(names) else "", "pod_id": pod, "requests": n,
+                        "breaches": b, "share": round(b / breaches, 4) if breaches else 0.0,
+                        "ttft_mean_ms": round(int(r["sum_milli"]) * 1e-3 / n, 3) if n else None,
+                        "ttft_max_ms": round(mx, 3) if math.isfinite(mx) else None})
+        return {"seen": int(res["pod_rec_pods"][g]), "breaching": int(res["pod_rec_pods_b"][g]),
+                "requests": int(res["pod_rec_n"][g]), "breaches": breaches, "top": top}
 
     def _exemplar_ids(self, res: dict, g: int) -> dict:
         """``request_ids`` (span ids) and ``trace_ids`` (de-duplicated, order kept) of group g's recent
@@ -856,6 +878,8 @@ class Agent:
             self.metrics.observe_ttft(res, head["ttft_sketch"], names)
         if head.get("exemplars") is not None and res.get("ex_n") is not None:
             self.metrics.observe_exemplars(res, head["exemplars"], names)
+        if head.get("pod_breakdown") is not None and res.get("pod_rec_pods") is not None:
+            self.metrics.observe_pods(res, head["pod_breakdown"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -970,6 +994,9 @@ class Agent:
         if o.request_exemplars and N > 1:
             raise ValueError("--request-exemplars runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the exemplar tracker's are read on the host")
+        if o.pod_breakdown and N > 1:
+            raise ValueError("--pod-breakdown runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the pod-breakdown tracker's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1016,7 +1043,9 @@ class Agent:
                             open_requests=int(o.open_requests_cap) if o.deadline_breach else 0,
                             open_reorder_ms=2.0 * float(o.window_ms),
                             sli_sketch=self.ttft_horizon() if o.ttft_distribution else 0,
-                            exemplars=int(o.request_exemplars), exemplar_windows=int(o.exemplar_windows))
+                            exemplars=int(o.request_exemplars), exemplar_windows=int(o.exemplar_windows),
+                            pod_breakdown=int(o.pod_breakdown), pod_windows=int(o.pod_breakdown_windows),
+                            pod_pairs=int(o.pod_pairs))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

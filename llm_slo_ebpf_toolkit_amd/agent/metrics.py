@@ -124,6 +124,21 @@ class AgentMetrics:
                                          "Request-exemplar events: invalid (a counted record with a NaN or negative "
                                          "TTFT), out_of_group (an SLI record of a group beyond the window's).",
                                          ("reason",))
+        # pod breakdown (agent --pod-breakdown, pipeline/podrank.py), over the recent windows. No per-pod
+        # label series: the label set would churn with every rollout
+        self.pods_seen = r.gauge("llm_slo_agent_pods_seen",
+                                 "Distinct pods with a counted request over the recent windows, by service.", ("service",))
+        self.pods_breaching = r.gauge("llm_slo_agent_pods_breaching",
+                                      "Distinct pods with at least one TTFT breach over the recent windows, by service.",
+                                      ("service",))
+        self.top_pod_share = r.gauge("llm_slo_agent_breach_top_pod_share",
+                                     "Share of the service's recent TTFT breaches on its worst pod (0 without a "
+                                     "breach): near 1 = one replica, near 1/pods = service-wide.", ("service",))
+        self.pod_events = r.counter("llm_slo_agent_pod_breakdown_events_total",
+                                    "Pod-breakdown events: invalid (a counted record with a NaN or negative TTFT), "
+                                    "out_of_group (an SLI record of a group beyond the window's), pod_out_of_range (a "
+                                    "pod id of 2^20 or more, in no pod row), pair_overflow (a record whose (service, "
+                                    "pod) pair found no place among the window's --pod-pairs).", ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -272,6 +287,21 @@ class AgentMetrics:
                 self.ttft_max.set(v, names[g] if g < len(names) else f"group-{g}")
         for reason in EVENT_STATS:
             self.exemplar_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_pods(self, res: dict, stats: dict, names) -> None:
+        """One window of the pod-breakdown tracker: ``res`` carries the pod_rec_* arrays per group
+        (pipeline/podrank.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.podrank import EVENT_STATS
+
+        for g, seen in enumerate(np.asarray(res["pod_rec_pods"]).tolist()):
+            name = names[g] if g < len(names) else f"group-{g}"
+            breaches = int(res["pod_rec_b"][g])
+            self.pods_seen.set(float(seen), name)
+            self.pods_breaching.set(float(res["pod_rec_pods_b"][g]), name)
+            worst = int(res["pod_rec_top"][g][0]["b"]) if int(res["pod_rec_k_top"][g]) else 0
+            self.top_pod_share.set(worst / breaches if breaches else 0.0, name)
+        for reason in EVENT_STATS:
+            self.pod_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

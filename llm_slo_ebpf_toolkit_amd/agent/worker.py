@@ -84,6 +84,13 @@ class WorkerSpec:
     sli_sketch: int = 0         # windows of the TTFT sketch's rolling horizon (agent --ttft-distribution); 0: off
     exemplars: int = 0          # worst-TTFT exemplars per service (agent --request-exemplars); 0: off
     exemplar_windows: int = 3   # windows of their horizon (agent --exemplar-windows)
+    pod_breakdown: int = 0      # ranked pods per service (agent --pod-breakdown); 0: off
+    pod_windows: int = 3        # windows of the recent scope (agent --pod-breakdown-windows)
+    pod_pairs: int = 4096       # distinct (service, pod) pairs a window may hold (agent --pod-pairs)
+
+
+# the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
+POD_RESULT_KEYS = tuple(f"pod_{s}_{f}" for s in ("win", "rec") for f in ("n", "b", "pods", "pods_b", "k_top", "top"))
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -98,7 +105,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
-                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent"):
+                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -168,7 +175,9 @@ class WorkerCore:
                                    group=group, model_image=np.frombuffer(spec.model_image, dtype=np.uint8),
                                    split_rings=spec.split, open_requests=spec.open_requests,
                                    open_reorder_ms=spec.open_reorder_ms, sli_sketch=spec.sli_sketch,
-                                   exemplars=spec.exemplars, exemplar_windows=spec.exemplar_windows)
+                                   exemplars=spec.exemplars, exemplar_windows=spec.exemplar_windows,
+                                   pod_breakdown=spec.pod_breakdown, pod_windows=spec.pod_windows,
+                                   pod_pairs=spec.pod_pairs)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -296,6 +305,10 @@ class WorkerCore:
                 from ..pipeline.exemplars import stats_dict as exemplar_stats
 
                 d["exemplars"] = exemplar_stats(pipe.exemplar_results(k, n_groups)["stats"])
+            if pipe.pods is not None:  # the pod-breakdown tracker's statistics of the window
+                from ..pipeline.podrank import stats_dict as pod_stats
+
+                d["pod_breakdown"] = pod_stats(pipe.pod_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

@@ -126,6 +126,14 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                                    "off); one GPU only; the horizon is not checkpointed"),
         ("exemplar-windows", d.exemplar_windows, "--request-exemplars: windows the recent exemplars look back over "
                                                  "(1..16; 3 = the span of the emission gate's burn)"),
+        ("pod-breakdown", d.pod_breakdown, "gpu engine: per service, the pods seen, the pods breaching the TTFT SLO "
+                                           "and this many pods with the most breaches, of the window and of the "
+                                           "last windows, ranked on the GPU -- a pods field in the decision log, "
+                                           "llm_slo_agent_pods_seen / _pods_breaching / _breach_top_pod_share"
+                                           "{service} (1..8; 0 = off); one GPU only; the horizon is not checkpointed"),
+        ("pod-breakdown-windows", d.pod_breakdown_windows, "--pod-breakdown: windows the recent scope looks back over "
+                                                           "(1..16; 3 = the span of the emission gate's burn)"),
+        ("pod-pairs", d.pod_pairs, "--pod-breakdown: distinct (service, pod) pairs one window may hold (1..2^20)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -177,6 +185,8 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         open_requests_cap=int(a.open_requests_cap),
         ttft_distribution=bool(a.ttft_distribution), ttft_horizon_windows=int(a.ttft_horizon_windows),
         request_exemplars=int(a.request_exemplars), exemplar_windows=int(a.exemplar_windows),
+        pod_breakdown=int(a.pod_breakdown), pod_breakdown_windows=int(a.pod_breakdown_windows),
+        pod_pairs=int(a.pod_pairs),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

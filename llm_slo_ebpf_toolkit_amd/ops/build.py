@@ -115,7 +115,8 @@ def build_hip_ext(force: bool = False, jobs: int = 4) -> str:
     return out
 
 
-AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip", "openreq.hip", "slisketch.hip", "exemplars.hip"]
+AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip", "openreq.hip", "slisketch.hip", "exemplars.hip",
+                 "podrank.hip"]
 
 
 def build_agent_ext(force: bool = False, jobs: int = 4) -> str:

@@ -12,6 +12,7 @@
 #include "engine.h"
 #include "exemplars.h"
 #include "openreq.h"
+#include "podrank.h"
 #include "slisketch.h"
 
 namespace py = pybind11;
@@ -542,6 +543,103 @@ class PyExemplarTracker {
   std::unique_ptr<ExemplarTracker> t_;
 };
 
+// The per-pod breach breakdown (podrank.h): one step per window over the same span ranges the
+// engine gets; results per step index. Rows leave as bytes [.., 32] (pipeline/podrank.py POD_ROW).
+class PyPodRankTracker {
+ public:
+  PyPodRankTracker(int device, int k, int windows, int64_t pair_cap, int64_t span_cap, int group_cap, int n_buffers,
+                   double slo_ms, bool lds) {
+    if (span_cap < 1 || span_cap >= (int64_t(1) << 31))
+      throw std::invalid_argument("pod breakdown: span_cap must be >= 1 and span_cap * windows < 2^22");
+    if (pair_cap < 1 || pair_cap > podrank::kMaxPairCap)
+      throw std::invalid_argument("pod breakdown: pair_cap must be in [1, 2^20]");
+    podrank::Config c;
+    c.device = device;
+    c.k = k;
+    c.windows = windows;
+    c.pair_cap = (int)pair_cap;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.slo_ms = slo_ms;
+    c.lds = lds;
+    podrank::validate(c);
+    t_ = std::make_unique<PodRankTracker>(c);
+  }
+  PodRankTracker& t() {
+    if (!t_) throw std::logic_error("pod breakdown closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    PodRankTracker& pr = t();
+    py::gil_scoped_release nogil;
+    return pr.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    PodRankTracker& pr = t();
+    if (n_groups < 0 || n_groups > pr.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = pr.results(i);
+    }
+    const podrank::Layout& l = pr.result_layout();
+    const py::ssize_t G = n_groups, K = pr.config().k;
+    static const char* scope[2] = {"win", "rec"};
+    py::dict d;
+    for (int s = 0; s < 2; ++s) {
+      const std::string p = std::string(scope[s]) + "_";
+      d[py::str(p + "n")] = copy_array(r + l.n[s], {G});
+      d[py::str(p + "b")] = copy_array(r + l.b[s], {G});
+      d[py::str(p + "pods")] = copy_array(r + l.pods[s], {G});
+      d[py::str(p + "pods_b")] = copy_array(r + l.pods_b[s], {G});
+      d[py::str(p + "k_top")] = copy_array(r + l.k_top[s], {G});
+      d[py::str(p + "top")] = copy_array(reinterpret_cast<const uint8_t*>(r + l.top[s]), {G, K, podrank::kRowBytes});
+    }
+    d["stats"] = copy_array(r + l.stats, {podrank::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // per horizon slot: (pair keys u64, n, b, max bits, sum_milli u64)
+  py::list resident() {
+    PodRankTracker& pr = t();
+    std::vector<podrank::PairList> h;
+    {
+      py::gil_scoped_release nogil;
+      h = pr.resident();
+    }
+    py::list out;
+    for (const podrank::PairList& l : h) {
+      const py::ssize_t n = (py::ssize_t)l.key.size();
+      out.append(py::make_tuple(copy_array(reinterpret_cast<const uint64_t*>(l.key.data()), {n}), copy_array(l.n.data(), {n}),
+                                copy_array(l.b.data(), {n}), copy_array(l.max.data(), {n}),
+                                copy_array(reinterpret_cast<const uint64_t*>(l.sum.data()), {n})));
+    }
+    return out;
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<PodRankTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -623,6 +721,23 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyExemplarTracker::resident)
       .def("sync", &PyExemplarTracker::sync)
       .def("close", &PyExemplarTracker::close);
+  m.attr("PODRANK_MAX_K") = podrank::kMaxK;
+  m.attr("PODRANK_MAX_H") = podrank::kMaxH;
+  m.attr("PODRANK_ROW_BYTES") = podrank::kRowBytes;
+  m.attr("PODRANK_STATS") = (int)podrank::kStats;
+  m.attr("PODRANK_LDS_SLOTS") = podrank::kLdsSlots;
+  m.def("podrank_slot_of", [](uint32_t g, uint32_t pod, uint32_t slots) { return podrank::slot_of(g, pod, slots); });
+  py::class_<PyPodRankTracker>(m, "PodRankTracker")
+      .def(py::init<int, int, int, int64_t, int64_t, int, int, double, bool>(), py::arg("device") = 0, py::arg("k") = 3,
+           py::arg("windows") = 3, py::arg("pair_cap") = 4096, py::arg("span_cap") = 16384, py::arg("group_cap") = 64,
+           py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("lds") = true)
+      .def("step", &PyPodRankTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyPodRankTracker::query)
+      .def("results", &PyPodRankTracker::results)
+      .def("step_ms", &PyPodRankTracker::step_ms)
+      .def("resident", &PyPodRankTracker::resident)
+      .def("sync", &PyPodRankTracker::sync)
+      .def("close", &PyPodRankTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -97,7 +97,7 @@ class WindowPipeline:
                  engine: str = "gpu", group=None, model_image: Optional[np.ndarray] = None, halo_windows: int = 3,
                  split_rings: bool = False, open_requests: int = 0, open_ttl_ms: float = 120000.0,
                  open_reorder_ms: Optional[float] = None, sli_sketch: int = 0, exemplars: int = 0,
-                 exemplar_windows: int = 3):
+                 exemplar_windows: int = 3, pod_breakdown: int = 0, pod_windows: int = 3, pod_pairs: int = 4096):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -120,7 +120,12 @@ class WindowPipeline:
         ``exemplars`` > 0: keep, per service, that many records with the largest TTFT of every window
         and of the last ``exemplar_windows`` windows (pipeline/exemplars.py; the device tracker for
         "gpu", the host oracle for "cpu"); ``results()`` then also carries ``ex_n`` / ``ex_k_win`` /
-        ``ex_win`` / ``ex_k_recent`` / ``ex_recent``. 0: off, nothing is constructed. One GPU only."""
+        ``ex_win`` / ``ex_k_recent`` / ``ex_recent``. 0: off, nothing is constructed. One GPU only.
+        ``pod_breakdown`` > 0: per service, count the pods seen and the pods breaching the TTFT SLO and
+        rank that many pods by breaches, for every window and for the last ``pod_windows`` windows,
+        with at most ``pod_pairs`` distinct (service, pod) pairs a window (pipeline/podrank.py; the
+        device tracker for "gpu", the host oracle for "cpu"); ``results()`` then also carries the
+        ``pod_*`` keys (podrank.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -224,6 +229,22 @@ class WindowPipeline:
                 from .exemplars import ExemplarOracle
 
                 self.exemplars = ExemplarOracle(**ekw)
+        self.pods = None
+        self._pod: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if pod_breakdown:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the pod breakdown runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            pkw = dict(k=int(pod_breakdown), windows=int(pod_windows), pair_cap=int(pod_pairs), span_cap=span_cap,
+                       group_cap=group_cap, n_buffers=self.nb, slo_ms=ttft_slo_ms, device=device)
+            if engine == "gpu":
+                from ..ops.podrank import PodRankTracker
+
+                self.pods = PodRankTracker(**pkw)
+            else:
+                from .podrank import PodRankOracle
+
+                self.pods = PodRankOracle(**pkw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -312,6 +333,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(exemplar_keys(self.exemplar_results(k, n_groups)))
+        if self.pods is not None:
+            from .podrank import result_keys as pod_keys
+
+            res = dict(res)
+            res.update(pod_keys(self.pod_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -373,9 +399,29 @@ class WindowPipeline:
 
         return empty_result(n_groups, self.exemplars.k)
 
+    # ---- pod breakdown (pipeline/podrank.py) ------------------------------------------------
+    def track_pods(self, spans, n_groups: int) -> None:
+        """The pod-breakdown tracker's step for the window about to be submitted: the same span
+        ranges. Every window steps (the horizon is counted in windows)."""
+        if self.pods is None:
+            return
+        self._pod[self.k % self.nb] = (self.k, self.pods.step(list(spans), int(n_groups)))
+
+    def pod_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The pod-breakdown tracker's results of window k (pipeline/podrank.py RESULT_FIELDS; an
+        empty step's for a window that was submitted past ``track_pods``)."""
+        held = self._pod.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.pods.results(held[1], n_groups)
+        from .podrank import empty_result
+
+        return empty_result(n_groups, self.pods.k)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.pods is not None:
+            self.pods.close()
         if self.exemplars is not None:
             self.exemplars.close()
         if self.sketch is not None:
@@ -422,6 +468,8 @@ class WindowPipeline:
             self.sketch.sync()
         if self.exemplars is not None:
             self.exemplars.sync()
+        if self.pods is not None:
+            self.pods.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -726,6 +774,8 @@ class RingWindowSource:
             pipe.track_sli(spans, n_groups)
         if pipe.exemplars is not None:  # and so do the request exemplars
             pipe.track_exemplars(spans, n_groups)
+        if pipe.pods is not None:  # and the pod breakdown
+            pipe.track_pods(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
