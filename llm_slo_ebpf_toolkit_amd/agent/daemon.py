@@ -226,6 +226,14 @@ class AgentOptions:
     pod_breakdown: int = 0               # ranked pods per service (1..8; 0: off)
     pod_breakdown_windows: int = 3       # windows the recent scope looks back over (burn.current's span)
     pod_pairs: int = 4096                # distinct (service, pod) pairs a window may hold
+    # per service, when the current run of TTFT breaches began: requests and breaches binned by the records' own
+    # start time into a ring on the GPU and a CUSUM over it (pipeline/onset.py): an onset field in the decision
+    # log and three series; one GPU; nothing is checkpointed (the ring refills over --onset-bins bins)
+    breach_onset: bool = False
+    onset_bin_ms: float = 0.0            # a bin's length (0: window_ms / 16, at least 1 ms)
+    onset_bins: int = 1024               # bins of the ring per service (a power of two in 64..8192)
+    onset_ref_burn: float = 2.0          # the CUSUM's reference breach rate, in error-budget multiples (untuned)
+    onset_alarm_breaches: int = 3        # excess breaches over the reference rate that count as an alarm (untuned)
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -749,6 +757,8 @@ class Agent:
                        and g < len(res["ex_recent"]) else {}),
                     **({"pods": self._pod_entry(res, g)} if res.get("pod_rec_top") is not None
                        and g < len(res["pod_rec_top"]) else {}),
+                    **({"onset": self._onset_entry(res, g, t_ns)} if res.get("onset_rows") is not None
+                       and g < len(res["onset_rows"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -807,6 +817,32 @@ class Agent:
                         "ttft_max_ms": round(mx, 3) if math.isfinite(mx) else None})
         return {"seen": int(res["pod_rec_pods"][g]), "breaching": int(res["pod_rec_pods_b"][g]),
                 "requests": int(res["pod_rec_n"][g]), "breaches": breaches, "top": top}
+
+    def onset_bin_ns(self) -> int:
+        """A bin of the breach-onset ring, ns: the flag, or a sixteenth of the window; 1 ms at least."""
+        ms = float(self.o.onset_bin_ms)
+        return max(1_000_000, int(round((ms if ms > 0 else float(self.o.window_ms) / 16.0) * 1e6)))
+
+    def onset_ref_ppm(self) -> int:
+        """The CUSUM's reference breach rate: --onset-ref-burn times the error budget, in millionths."""
+        from ..pipeline.onset import ref_ppm_of
+
+        return ref_ppm_of(self.o.onset_ref_burn, self.o.slo_target)
+
+    def _onset_entry(self, res: dict, g: int, t_ns: int) -> dict:
+        """Group g's breach onset for the decision log: times are bin starts, ``age_ms`` = the cut minus
+        the onset, ``delay_ms`` = the alarm minus the onset, ``excess`` = breaches over the reference rate."""
+        from ..pipeline.onset import CLIPPED
+
+        r, bin_ns = res["onset_rows"][g], self.onset_bin_ns()
+        state, onset_q, alarm_q = int(r["state"]), int(r["onset_q"]), int(r["alarm_q"])
+        onset_ts = onset_q * bin_ns if state else None
+        alarm_ts = alarm_q * bin_ns if state and alarm_q >= 0 else None
+        return {"state": state, "onset_ts_ns": onset_ts, "alarm_ts_ns": alarm_ts,
+                "age_ms": round((int(t_ns) - onset_ts) * 1e-6, 3) if state else None,
+                "delay_ms": round((alarm_ts - onset_ts) * 1e-6, 3) if alarm_ts is not None else None,
+                "excess": round(int(r["s_now"]) * 1e-6, 6), "requests": int(r["n_exc"]), "breaches": int(r["b_exc"]),
+                "clipped": bool(int(r["flags"]) & CLIPPED)}
 
     def _exemplar_ids(self, res: dict, g: int) -> dict:
         """``request_ids`` (span ids) and ``trace_ids`` (de-duplicated, order kept) of group g's recent
@@ -880,6 +916,8 @@ class Agent:
             self.metrics.observe_exemplars(res, head["exemplars"], names)
         if head.get("pod_breakdown") is not None and res.get("pod_rec_pods") is not None:
             self.metrics.observe_pods(res, head["pod_breakdown"], names)
+        if head.get("breach_onset") is not None and res.get("onset_rows") is not None:
+            self.metrics.observe_onset(res, head["breach_onset"], names, t_ns, self.onset_bin_ns())
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -997,6 +1035,9 @@ class Agent:
         if o.pod_breakdown and N > 1:
             raise ValueError("--pod-breakdown runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the pod-breakdown tracker's are read on the host")
+        if o.breach_onset and N > 1:
+            raise ValueError("--breach-onset runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the breach-onset tracker's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1045,7 +1086,10 @@ class Agent:
                             sli_sketch=self.ttft_horizon() if o.ttft_distribution else 0,
                             exemplars=int(o.request_exemplars), exemplar_windows=int(o.exemplar_windows),
                             pod_breakdown=int(o.pod_breakdown), pod_windows=int(o.pod_breakdown_windows),
-                            pod_pairs=int(o.pod_pairs))
+                            pod_pairs=int(o.pod_pairs),
+                            breach_onset=int(o.onset_bins) if o.breach_onset else 0,
+                            onset_bin_ns=self.onset_bin_ns(), onset_ref_ppm=self.onset_ref_ppm(),
+                            onset_alarm=int(o.onset_alarm_breaches))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

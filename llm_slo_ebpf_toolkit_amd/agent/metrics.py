@@ -139,6 +139,19 @@ class AgentMetrics:
                                     "out_of_group (an SLI record of a group beyond the window's), pod_out_of_range (a "
                                     "pod id of 2^20 or more, in no pod row), pair_overflow (a record whose (service, "
                                     "pod) pair found no place among the window's --pod-pairs).", ("reason",))
+        # breach onset (agent --breach-onset, pipeline/onset.py): when the current run of breaches began
+        self.onset_age = r.gauge("llm_slo_agent_breach_onset_age_seconds",
+                                 "Seconds from the onset of the service's current TTFT breach excursion (CUSUM over "
+                                 "time bins of the requests' start times, on the GPU) to the window's cut; 0 when quiet.",
+                                 ("service",))
+        self.onset_state = r.gauge("llm_slo_agent_breach_onset_state",
+                                   "Breach-onset state by service: 0 quiet, 1 excursion, 2 alarm (the excursion has "
+                                   "reached --onset-alarm-breaches over the reference rate).", ("service",))
+        self.onset_events = r.counter("llm_slo_agent_breach_onset_events_total",
+                                      "Breach-onset events: invalid (a counted record with a NaN or negative TTFT), "
+                                      "out_of_group (an SLI record of a group beyond the window's), no_time (no start "
+                                      "time, in no bin), future (a start time past the cut, placed in the newest bin), "
+                                      "too_old (a start time before the ring, placed nowhere).", ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -302,6 +315,21 @@ class AgentMetrics:
             self.top_pod_share.set(worst / breaches if breaches else 0.0, name)
         for reason in EVENT_STATS:
             self.pod_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_onset(self, res: dict, stats: dict, names, t_ns: int, bin_ns: int) -> None:
+        """One window of the breach-onset tracker: ``res`` carries ``onset_rows`` per group
+        (pipeline/onset.py ONSET_ROW), ``stats`` by name; ``t_ns`` the window's cut, ``bin_ns`` a bin."""
+        from ..pipeline.onset import EVENT_STATS
+
+        rows = res["onset_rows"]
+        for g in range(len(rows)):
+            name = names[g] if g < len(names) else f"group-{g}"
+            state = int(rows[g]["state"])
+            age = max(0.0, (int(t_ns) - int(rows[g]["onset_q"]) * int(bin_ns)) * 1e-9) if state else 0.0
+            self.onset_age.set(age, name)
+            self.onset_state.set(float(state), name)
+        for reason in EVENT_STATS:
+            self.onset_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

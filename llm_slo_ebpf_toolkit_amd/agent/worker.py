@@ -87,6 +87,10 @@ class WorkerSpec:
     pod_breakdown: int = 0      # ranked pods per service (agent --pod-breakdown); 0: off
     pod_windows: int = 3        # windows of the recent scope (agent --pod-breakdown-windows)
     pod_pairs: int = 4096       # distinct (service, pod) pairs a window may hold (agent --pod-pairs)
+    breach_onset: int = 0       # bins of the breach-onset ring per service (agent --breach-onset, --onset-bins); 0: off
+    onset_bin_ns: int = 125_000_000  # a bin's length (agent --onset-bin-ms)
+    onset_ref_ppm: int = 20000  # the CUSUM's reference breach rate, millionths (agent --onset-ref-burn)
+    onset_alarm: int = 3        # excess breaches that count as an alarm (agent --onset-alarm-breaches)
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
@@ -105,7 +109,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
-                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS):
+                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -177,7 +181,9 @@ class WorkerCore:
                                    open_reorder_ms=spec.open_reorder_ms, sli_sketch=spec.sli_sketch,
                                    exemplars=spec.exemplars, exemplar_windows=spec.exemplar_windows,
                                    pod_breakdown=spec.pod_breakdown, pod_windows=spec.pod_windows,
-                                   pod_pairs=spec.pod_pairs)
+                                   pod_pairs=spec.pod_pairs, breach_onset=spec.breach_onset,
+                                   onset_bin_ns=spec.onset_bin_ns, onset_ref_ppm=spec.onset_ref_ppm,
+                                   onset_alarm=spec.onset_alarm)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -309,6 +315,10 @@ class WorkerCore:
                 from ..pipeline.podrank import stats_dict as pod_stats
 
                 d["pod_breakdown"] = pod_stats(pipe.pod_results(k, n_groups)["stats"])
+            if pipe.onset is not None:  # the breach-onset tracker's statistics of the window
+                from ..pipeline.onset import stats_dict as onset_stats
+
+                d["breach_onset"] = onset_stats(pipe.onset_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

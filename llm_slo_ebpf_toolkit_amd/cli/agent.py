@@ -134,6 +134,18 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         ("pod-breakdown-windows", d.pod_breakdown_windows, "--pod-breakdown: windows the recent scope looks back over "
                                                            "(1..16; 3 = the span of the emission gate's burn)"),
         ("pod-pairs", d.pod_pairs, "--pod-breakdown: distinct (service, pod) pairs one window may hold (1..2^20)"),
+        ("breach-onset", False, "gpu engine: per service, when the current run of TTFT breaches began -- requests and "
+                                "breaches binned by the records' own start time into a ring on the GPU, a CUSUM over "
+                                "it every window -- an onset field in the decision log, "
+                                "llm_slo_agent_breach_onset_age_seconds / _state{service}; one GPU only; the ring is "
+                                "not checkpointed"),
+        ("onset-bin-ms", d.onset_bin_ms, "--breach-onset: a time bin's length (0 = window-ms / 16; at least 1)"),
+        ("onset-bins", d.onset_bins, "--breach-onset: bins of the ring per service (a power of two in 64..8192)"),
+        ("onset-ref-burn", d.onset_ref_burn, "--breach-onset: the CUSUM's reference breach rate, in error-budget "
+                                             "multiples (untuned: midway between on budget and a 3x page)"),
+        ("onset-alarm-breaches", d.onset_alarm_breaches, "--breach-onset: excess breaches over the reference rate "
+                                                         "that count as an alarm (untuned: one slow request cannot "
+                                                         "reach 3)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -187,6 +199,8 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         request_exemplars=int(a.request_exemplars), exemplar_windows=int(a.exemplar_windows),
         pod_breakdown=int(a.pod_breakdown), pod_breakdown_windows=int(a.pod_breakdown_windows),
         pod_pairs=int(a.pod_pairs),
+        breach_onset=bool(a.breach_onset), onset_bin_ms=float(a.onset_bin_ms), onset_bins=int(a.onset_bins),
+        onset_ref_burn=float(a.onset_ref_burn), onset_alarm_breaches=int(a.onset_alarm_breaches),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -11,6 +11,7 @@
 
 #include "engine.h"
 #include "exemplars.h"
+#include "onset.h"
 #include "openreq.h"
 #include "podrank.h"
 #include "slisketch.h"
@@ -640,6 +641,90 @@ class PyPodRankTracker {
   std::unique_ptr<PodRankTracker> t_;
 };
 
+// The breach-onset tracker (onset.h): one step per timed window cut over the same span ranges the
+// engine gets; results per step index. Rows leave as bytes [G, 64] (pipeline/onset.py ONSET_ROW).
+class PyOnsetTracker {
+ public:
+  PyOnsetTracker(int device, int64_t bins, int64_t bin_ns, int64_t ref_ppm, int64_t alarm, int64_t span_cap, int group_cap,
+                 int n_buffers, double slo_ms, int64_t ring_records_max, bool lds) {
+    if (bins < onset::kMinBins || bins > onset::kMaxBins)
+      throw std::invalid_argument("breach onset: bins must be a power of two in [64, 8192]");
+    if (span_cap < 1) throw std::invalid_argument("breach onset: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("breach onset: the ring needs more than 2 GiB");
+    onset::Config c;
+    c.device = device;
+    c.bins = (int)bins;
+    c.bin_ns = bin_ns;
+    c.ref_ppm = ref_ppm;
+    c.alarm = alarm;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.slo_ms = slo_ms;
+    c.ring_records_max = ring_records_max;
+    c.lds = lds;
+    onset::validate(c);
+    t_ = std::make_unique<OnsetTracker>(c);
+  }
+  OnsetTracker& t() {
+    if (!t_) throw std::logic_error("breach onset closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
+    OnsetTracker& on = t();
+    py::gil_scoped_release nogil;
+    return on.step(spans, cut_ns, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    OnsetTracker& on = t();
+    if (n_groups < 0 || n_groups > on.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = on.results(i);
+    }
+    const onset::Layout& l = on.result_layout();
+    py::dict d;
+    d["rows"] = copy_array(reinterpret_cast<const uint8_t*>(r + l.rows), {(py::ssize_t)n_groups, onset::kRowBytes});
+    d["stats"] = copy_array(r + l.stats, {onset::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (cells u64 [group_cap, bins] in slot order, q_hi)
+  py::tuple resident() {
+    OnsetTracker& on = t();
+    onset::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = on.resident();
+    }
+    return py::make_tuple(copy_array(reinterpret_cast<const uint64_t*>(h.cells.data()),
+                                     {(py::ssize_t)on.config().group_cap, (py::ssize_t)on.config().bins}),
+                          h.q_hi);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<OnsetTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -738,6 +823,23 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyPodRankTracker::resident)
       .def("sync", &PyPodRankTracker::sync)
       .def("close", &PyPodRankTracker::close);
+  m.attr("ONSET_ROW_BYTES") = onset::kRowBytes;
+  m.attr("ONSET_STATS") = (int)onset::kStats;
+  m.attr("ONSET_LDS_SLOTS") = onset::kLdsSlots;
+  m.attr("ONSET_BINS") = py::make_tuple(onset::kMinBins, onset::kMaxBins);
+  py::class_<PyOnsetTracker>(m, "OnsetTracker")
+      .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, double, int64_t, bool>(),
+           py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_ns") = (int64_t)125000000,
+           py::arg("ref_ppm") = (int64_t)20000, py::arg("alarm") = (int64_t)3, py::arg("span_cap") = 16384,
+           py::arg("group_cap") = 64, py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0,
+           py::arg("ring_records_max") = onset::kMaxRingRecords, py::arg("lds") = true)
+      .def("step", &PyOnsetTracker::step, py::arg("spans"), py::arg("cut_ns"), py::arg("n_groups"))
+      .def("query", &PyOnsetTracker::query)
+      .def("results", &PyOnsetTracker::results)
+      .def("step_ms", &PyOnsetTracker::step_ms)
+      .def("resident", &PyOnsetTracker::resident)
+      .def("sync", &PyOnsetTracker::sync)
+      .def("close", &PyOnsetTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -1,0 +1,83 @@
+// Breach onset per service: when the current run of TTFT breaches began, at sub-window resolution.
+//
+// Every other reduction is per window, so the finest time known for a fault is the window it first
+// scored in, and a breach exported late counts in the window it arrives in. This side tracker bins
+// the counted span records by their own start time (Span::ts_ns) into a ring of B absolute time bins
+// per service (onset_host.h: bin_of, slot_of, place), one u64 cell of (requests, breaches) a bin, and
+// recomputes an integer CUSUM over the whole ring every step, so a late record revises the past.
+// Per service it yields the onset of the current excursion, the bin an online detector would have
+// fired in, and the excess since then (onset_host.h Row). Nothing is kept between steps but the ring:
+// the result is a pure function of the ring and the parameters. Integers only, so host and device
+// agree bit for bit. The engine, its graphs and its streams are not touched. pipeline/onset.py holds
+// the same rules in numpy (the oracle, and what the CPU engine uses).
+//
+// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window with a timed cut:
+//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
+//            returns: the rings' release contract stays the engine's),
+//   advance  clear the slots of the bins (previous q_hi, q_hi] in every row; not launched when q_hi
+//            did not move,
+//   observe  one thread per record: one 64-bit add into its (service, slot) cell; with `lds` every
+//            workgroup aggregates its cells in an LDS table first,
+//   scan     one wave per service row, every row of group_cap: the CUSUM as a wave scan of
+//            (sum, minimum prefix) pairs (onset_host.h combine), then onset, alarm, peak and counts,
+//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "mislo_common.h"
+#include "onset_host.h"
+#include "openreq_host.h"
+
+namespace mislo {
+
+namespace onset {
+
+// the whole ring as the host reads it back, bins in slot order
+struct Resident {
+  std::vector<unsigned long long> cells;  // [group_cap][bins]
+  int64_t q_hi = kNoBin;
+};
+
+}  // namespace onset
+
+class OnsetTracker {
+ public:
+  explicit OnsetTracker(const onset::Config& cfg);
+  ~OnsetTracker();
+  OnsetTracker(const OnsetTracker&) = delete;
+  OnsetTracker& operator=(const OnsetTracker&) = delete;
+
+  // One window cut at cut_ns (> 0); returns the step's index. The ranges are read before it returns.
+  int64_t step(const std::vector<onset::Range>& spans, int64_t cut_ns, int n_groups);
+  bool query(int64_t i);
+  // the step's result block (onset::layout), valid until n_buffers later steps; waits for it
+  const uint32_t* results(int64_t i);
+  // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
+  std::vector<float> step_ms(int64_t i);
+  // the ring and q_hi (synchronous; tests)
+  onset::Resident resident();
+  void sync();
+  int64_t q_hi() const { return q_hi_; }
+  const onset::Config& config() const { return cfg_; }
+  const onset::Layout& result_layout() const { return lay_; }
+
+ private:
+  int slot_of(int64_t i) const;
+
+  onset::Config cfg_;
+  onset::Layout lay_;
+  openreq::SlotRing slots_;
+  onset::Population pop_;
+  int64_t q_hi_ = onset::kNoBin;
+  hipStream_t st_ = nullptr;
+  Span* spans_ = nullptr;
+  unsigned long long* ring_ = nullptr;  // [group_cap][bins] cells
+  uint32_t* block_ = nullptr;
+  std::vector<uint32_t*> host_;
+  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_advanced_, ev_observed_, ev_end_;
+};
+
+}  // namespace mislo

@@ -97,7 +97,9 @@ class WindowPipeline:
                  engine: str = "gpu", group=None, model_image: Optional[np.ndarray] = None, halo_windows: int = 3,
                  split_rings: bool = False, open_requests: int = 0, open_ttl_ms: float = 120000.0,
                  open_reorder_ms: Optional[float] = None, sli_sketch: int = 0, exemplars: int = 0,
-                 exemplar_windows: int = 3, pod_breakdown: int = 0, pod_windows: int = 3, pod_pairs: int = 4096):
+                 exemplar_windows: int = 3, pod_breakdown: int = 0, pod_windows: int = 3, pod_pairs: int = 4096,
+                 breach_onset: int = 0, onset_bin_ns: Optional[int] = None, onset_ref_ppm: int = 20000,
+                 onset_alarm: int = 3):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -125,7 +127,13 @@ class WindowPipeline:
         rank that many pods by breaches, for every window and for the last ``pod_windows`` windows,
         with at most ``pod_pairs`` distinct (service, pod) pairs a window (pipeline/podrank.py; the
         device tracker for "gpu", the host oracle for "cpu"); ``results()`` then also carries the
-        ``pod_*`` keys (podrank.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
+        ``pod_*`` keys (podrank.RESULT_KEYS). 0: off, nothing is constructed. One GPU only.
+        ``breach_onset`` > 0: per service, keep a ring of that many absolute time bins of ``onset_bin_ns``
+        (default ``window_ms`` / 16) of requests and breaches by the records' own start time, run a CUSUM
+        with the reference breach rate ``onset_ref_ppm`` (millionths) over it every window and report the
+        onset of the current excursion and the bin it reached ``onset_alarm`` excess breaches in
+        (pipeline/onset.py; the device tracker for "gpu", the host oracle for "cpu"); ``results()`` then
+        also carries ``onset_rows`` (onset.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -245,6 +253,24 @@ class WindowPipeline:
                 from .podrank import PodRankOracle
 
                 self.pods = PodRankOracle(**pkw)
+        self.onset = None
+        self.onset_skipped = 0  # cuts without a time (replay helpers): no tracker step
+        self._onset: Dict[int, Tuple[int, Optional[int]]] = {}  # buffer -> (window, tracker step)
+        if breach_onset:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the breach onset runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            bin_ns = max(1_000_000, int(round(window_ms * 1e6 / 16))) if onset_bin_ns is None else int(onset_bin_ns)
+            okw = dict(bins=int(breach_onset), bin_ns=bin_ns, ref_ppm=int(onset_ref_ppm), alarm=int(onset_alarm),
+                       span_cap=span_cap, group_cap=group_cap, n_buffers=self.nb, slo_ms=ttft_slo_ms, device=device)
+            if engine == "gpu":
+                from ..ops.onset import OnsetTracker
+
+                self.onset = OnsetTracker(**okw)
+            else:
+                from .onset import OnsetOracle
+
+                self.onset = OnsetOracle(**okw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -338,6 +364,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(pod_keys(self.pod_results(k, n_groups)))
+        if self.onset is not None:
+            from .onset import result_keys as onset_keys
+
+            res = dict(res)
+            res.update(onset_keys(self.onset_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -417,9 +448,34 @@ class WindowPipeline:
 
         return empty_result(n_groups, self.pods.k)
 
+    # ---- breach onset (pipeline/onset.py) ---------------------------------------------------
+    def track_onset(self, spans, cut_ns: int, n_groups: int) -> None:
+        """The breach-onset tracker's step for the window about to be submitted: the same span ranges
+        and the cut's time. A cut without a time is skipped and counted."""
+        if self.onset is None:
+            return
+        step = None
+        if int(cut_ns) > 0:
+            step = self.onset.step(list(spans), int(cut_ns), int(n_groups))
+        else:
+            self.onset_skipped += 1
+        self._onset[self.k % self.nb] = (self.k, step)
+
+    def onset_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The breach-onset tracker's results of window k (pipeline/onset.py RESULT_FIELDS; empty_result
+        for a window it skipped)."""
+        held = self._onset.get(k % self.nb)
+        if held is not None and held[0] == k and held[1] is not None:
+            return self.onset.results(held[1], n_groups)
+        from .onset import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.onset is not None:
+            self.onset.close()
         if self.pods is not None:
             self.pods.close()
         if self.exemplars is not None:
@@ -470,6 +526,8 @@ class WindowPipeline:
             self.exemplars.sync()
         if self.pods is not None:
             self.pods.sync()
+        if self.onset is not None:
+            self.onset.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -776,6 +834,8 @@ class RingWindowSource:
             pipe.track_exemplars(spans, n_groups)
         if pipe.pods is not None:  # and the pod breakdown
             pipe.track_pods(spans, n_groups)
+        if pipe.onset is not None:  # the breach onset sees the window's spans and the cut's time
+            pipe.track_onset(spans, cut.t_ns, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
