@@ -199,6 +199,7 @@ class WorkerCore:
         self.pending: Deque[Tuple[int, float, int]] = collections.deque()
         self.windows = 0
         self.collect_s = self.collect_wait_s = 0.0  # host time collecting finished windows / waiting for them
+        self.pipe.prepare_copy_ahead()  # window() stages in two halves there: the second copy lane
 
     @classmethod
     def adopt(cls, spec: WorkerSpec, pipe, src) -> "WorkerCore":
@@ -210,12 +211,15 @@ class WorkerCore:
         core.pending = collections.deque()
         core.windows = 0
         core.collect_s = core.collect_wait_s = 0.0
+        pipe.prepare_copy_ahead()
         return core
 
     @property
     def max_pending(self) -> int:
-        """Windows staged but not yet collected, at most: the engine's buffers minus the one the
-        next stage reuses (that window's results must have been read first)."""
+        """Windows staged but not yet collected, at most, when a window's chain is queued: the
+        engine's buffers minus the one that chain reuses (that window's results must have been
+        read first). In the plain order the oldest ones beyond it are collected right after the
+        stage; with copy-ahead right before the chain half, so up to nb wait between calls."""
         return max(1, int(self.pipe.nb) - 1)
 
     def window(self, cut, n_groups: int, pods=None, labels=None) -> dict:
@@ -226,9 +230,16 @@ class WorkerCore:
         window younger than that, so window k+1's copies are issued while windows k-1 and k
         compute (waiting for k-1 here put one window's copy time plus the host's turnaround on
         every window: profiles/r4_timeline/). ``labels``: incident labels for the device's
-        confusion matrix (the benchmark's replay windows; the agent has none)."""
+        confusion matrix (the benchmark's replay windows; the agent has none).
+
+        Where the pipeline offers ``copy_ahead`` (pipeline/window.py: overlapped windows on one GPU,
+        no side tracker) the window is staged in two halves around the only blocking collect
+        (``_window_copy_ahead``); everywhere else -- the CPU engine, several GPUs, trackers -- in
+        the order above."""
         if pods is not None and len(pods[0]):
             self.pipe.eng.set_pods(*pods)
+        if self.pipe.copy_ahead:
+            return self._window_copy_ahead(cut, n_groups, labels)
         t0 = time.perf_counter()
         r = self.src.stage(cut, n_groups, labels, with_labels=labels is not None, learn=False)
         host_us = 1e6 * (time.perf_counter() - t0)
@@ -237,6 +248,33 @@ class WorkerCore:
         prevs = []
         while len(self.pending) > 1 and (len(self.pending) > self.max_pending or
                                          self.pipe.eng.query(self.pending[0][0])):
+            prevs.append(self._collect(*self.pending.popleft()))
+        out["prevs"] = prevs
+        self.windows += 1
+        return out
+
+    def _window_copy_ahead(self, cut, n_groups: int, labels) -> dict:
+        """``window`` with window k's DMAs issued first: the copy half of window k (they write only
+        the data regions of buffer k % nb, which the front stage of window k - nb is through
+        with); then the oldest windows collected while more than ``max_pending`` would be
+        outstanding -- window k - nb, whose packet and results window k's chain overwrites: the
+        only blocking step, now behind the DMA issue instead of in front of the next window's;
+        then the chain half; then, as ever, whatever else is finished. Between calls up to nb
+        windows are therefore uncollected (nb - 1 in the plain order), and a finished window
+        still comes back with the first ``window`` or ``collect`` call after its chain is done."""
+        src = self.src
+        t0 = time.perf_counter()
+        src.stage_copy(cut, n_groups, labels)
+        t1 = time.perf_counter()
+        prevs = []
+        while len(self.pending) > self.max_pending:
+            prevs.append(self._collect(*self.pending.popleft()))
+        t2 = time.perf_counter()
+        r = src.stage_chain(with_labels=labels is not None, learn=False)
+        host_us = 1e6 * ((t1 - t0) + (time.perf_counter() - t2))
+        out = {"rank": self.spec.rank, "k": r["k"], "staged": r, "done": src.done()}
+        self.pending.append((r["k"], host_us, n_groups))
+        while len(self.pending) > 1 and self.pipe.eng.query(self.pending[0][0]):
             prevs.append(self._collect(*self.pending.popleft()))
         out["prevs"] = prevs
         self.windows += 1

@@ -86,10 +86,30 @@ class PyEngine {
     return e_->register_host(reinterpret_cast<const void*>(addr), bytes);
   }
   // segments: lists of (host address, bytes) in ring order
-  void submit(int64_t k, const std::vector<std::pair<uintptr_t, size_t>>& kernel,
-              const std::vector<std::pair<uintptr_t, size_t>>& user,
-              const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups, py::object labels,
-              std::vector<int64_t> bases, bool with_labels, bool learn, int user_rec) {
+  using Ranges = std::vector<std::pair<uintptr_t, size_t>>;
+  void submit(int64_t k, const Ranges& kernel, const Ranges& user, const Ranges& spans, int n_groups,
+              py::object labels, std::vector<int64_t> bases, bool with_labels, bool learn, int user_rec) {
+    std::vector<int32_t> lab;
+    const WindowInput in = window_input(kernel, user, spans, n_groups, labels, std::move(bases), user_rec, lab);
+    py::gil_scoped_release nogil;
+    e_->submit(k, in, with_labels, learn);
+  }
+  // the two phases of submit (engine.h): the window's DMAs, then its chain
+  void submit_copy(int64_t k, const Ranges& kernel, const Ranges& user, const Ranges& spans, int n_groups,
+                   py::object labels, std::vector<int64_t> bases, int user_rec) {
+    std::vector<int32_t> lab;
+    const WindowInput in = window_input(kernel, user, spans, n_groups, labels, std::move(bases), user_rec, lab);
+    py::gil_scoped_release nogil;
+    e_->submit_copy(k, in);
+  }
+  void submit_chain(int64_t k, int n_groups, bool with_labels, bool learn) {
+    py::gil_scoped_release nogil;
+    e_->submit_chain(k, n_groups, with_labels, learn);
+  }
+  // `lab` holds the labels the returned input points to
+  static WindowInput window_input(const Ranges& kernel, const Ranges& user, const Ranges& spans, int n_groups,
+                                  py::object labels, std::vector<int64_t> bases, int user_rec,
+                                  std::vector<int32_t>& lab) {
     WindowInput in;
     auto conv = [](const std::vector<std::pair<uintptr_t, size_t>>& v, std::vector<Seg>& out) {
       for (auto& p : v) out.push_back(Seg{reinterpret_cast<const void*>(p.first), p.second});
@@ -99,7 +119,6 @@ class PyEngine {
     conv(spans, in.spans);
     in.n_groups = n_groups;
     in.user_rec = user_rec;
-    std::vector<int32_t> lab;
     if (!labels.is_none()) {
       auto arr = labels.cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
       lab.assign(arr.data(), arr.data() + arr.size());
@@ -108,8 +127,7 @@ class PyEngine {
     }
     bases.resize(4, 0);
     for (int q = 0; q < 4; ++q) in.bases[q] = bases[q];
-    py::gil_scoped_release nogil;
-    e_->submit(k, in, with_labels, learn);
+    return in;
   }
   bool h2d_done(int64_t k) { return e_->h2d_done(k); }
   void wait_h2d(int64_t k) {
@@ -854,6 +872,11 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("submit", &PyEngine::submit, py::arg("k"), py::arg("kernel"), py::arg("user"), py::arg("spans"),
            py::arg("n_groups"), py::arg("labels") = py::none(), py::arg("bases") = std::vector<int64_t>{},
            py::arg("with_labels") = true, py::arg("learn") = false, py::arg("user_rec") = 64)
+      .def("submit_copy", &PyEngine::submit_copy, py::arg("k"), py::arg("kernel"), py::arg("user"), py::arg("spans"),
+           py::arg("n_groups"), py::arg("labels") = py::none(), py::arg("bases") = std::vector<int64_t>{},
+           py::arg("user_rec") = 64)
+      .def("submit_chain", &PyEngine::submit_chain, py::arg("k"), py::arg("n_groups"), py::arg("with_labels") = true,
+           py::arg("learn") = false)
       .def("h2d_done", &PyEngine::h2d_done)
       .def("wait_h2d", &PyEngine::wait_h2d)
       .def("query", &PyEngine::query)
@@ -889,6 +912,11 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("close", &PyEngine::close)
       .def_property_readonly("buffers", &PyEngine::buffers)
       .def_property_readonly("copy_lanes", [](PyEngine& p) { return p.eng().copy_lanes(); })
+      .def_property_readonly("copy_ahead", [](PyEngine& p) { return p.eng().copy_ahead(); })
+      .def("take_copy_lanes", [](PyEngine& p) {
+        py::gil_scoped_release nogil;
+        return p.eng().take_copy_lanes();
+      })
       .def_property_readonly("windows_folded", &PyEngine::folded)
       .def_property_readonly("graphs", &PyEngine::graphs)
       .def_property_readonly("host_issue_us", &PyEngine::host_issue_us)

@@ -1,6 +1,6 @@
 // Copy lanes: which copy stream a window's DMAs go to, and the host-side account of how far the
 // windows have been copied. Pure host arithmetic (no HIP), shared by the engine and by
-// tests/native/copylanes_host_check.cpp.
+// tests/native/copylanes_host_check.cpp and copyahead_host_check.cpp.
 //
 // A lane is one in-order copy stream. With two lanes window k's DMAs go to lane k & 1, so a lane
 // completes its windows in order (k, k - 2, k - 4, ...) but the two lanes complete in any order
@@ -27,17 +27,24 @@ inline int copy_consults(int64_t k, int lanes, int64_t out[kMaxCopyLanes]) {
   return n;
 }
 
+// The copy-side events of window k (the marker before its first DMA and its completion event)
+// live in slot k % (2 nb): the copy phase of window k + nb may run while window k has not been
+// collected, and that window's timing (window_ms, copy_ms) must still read its own records.
+inline int copy_mark_slots(int nb) { return 2 * nb; }
+inline int copy_mark_slot(int64_t k, int nb) { return (int)(k % copy_mark_slots(nb)); }
+
 // Every window below `n` is known copied; `n` only moves forward.
 //
-// A window's completion event lives in its buffer (k % nb) and is recorded again by window
-// k + nb. The engine synchronises that event before it records it again (the buffer's pinned
-// head and staging are rewritten then) and calls reused(): so the event of a window >= n still
-// belongs to that window, and a window < n is never asked about again -- no stale answer.
+// A window's completion event lives in its slot and is recorded again by window k + 2 nb. The
+// copy phase of window k + nb synchronises it first (the buffer's pinned head and staging are
+// rewritten then) and calls reused(): so the event of a window >= n still belongs to that window,
+// and a window < n is never asked about again -- no stale answer.
+// tests/native/copyahead_host_check.cpp walks this protocol.
 struct CopiedUpTo {
   int64_t n = 0;
 
-  // submit(k) synchronised window k - nb's event, as submit(k - 1) did window k - 1 - nb's: with
-  // every lane in order, every window <= k - nb has been copied
+  // the copy phase of window k synchronised window k - nb's event, as that of window k - 1 did
+  // window k - 1 - nb's: with every lane in order, every window <= k - nb has been copied
   void reused(int64_t k, int nb) {
     if (k - nb + 1 > n) n = k - nb + 1;
   }

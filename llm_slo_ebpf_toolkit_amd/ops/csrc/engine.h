@@ -154,19 +154,44 @@ class WindowEngine {
   // the driver refuses (those ranges then go through pinned staging).
   bool register_host(const void* ptr, size_t bytes);
   // Queue window k (in order). Returns when its DMAs and kernels are queued; the ring bytes
-  // must stay untouched until h2d_done(k).
+  // must stay untouched until h2d_done(k). The two phases below, back to back.
   void submit(int64_t k, const WindowInput& in, bool with_labels, bool learn);
+  // The two phases of submit, for a caller that reads the oldest window's results between them.
+  // Copy phase: the checks, the buffer's pinned head and staging, the window's DMAs on its copy
+  // lane. With copy_ahead() it does not wait for compute_done(k - max_ahead): the DMAs write only
+  // the data regions of the device block, which the front stage of window k - nb read last, so it
+  // waits for that window's front_done (and, as ever, its h2d_done and head_done) and the DMAs go
+  // out while windows k - nb .. k - 1 may still be computing. Window k - nb's packet and results
+  // stay readable until submit_chain(k).
+  void submit_copy(int64_t k, const WindowInput& in);
+  // Chain phase: the back-pressure on compute_done(k - max_ahead), the stream waits, the head
+  // load, the refit, the window's graphs and tail. It overwrites window k - nb's packet and
+  // results. n_groups as given to the copy phase.
+  void submit_chain(int64_t k, int n_groups, bool with_labels, bool learn);
+  // The copy phase may run ahead of the oldest window's results: overlapped windows only (not the
+  // serial chain, an engine sized for the exchange, after init_comm, MISLO_ONE_STREAM);
+  // MISLO_COPY_AHEAD=0|1 overrides the default where it is available.
+  bool copy_ahead() const { return copy_ahead_; }
   // the input DMAs of every window up to k completed (their ring space may be freed): never true
-  // for a window while an earlier one is still being read, whichever lane finishes first
+  // for a window while an earlier one is still being read, whichever lane finishes first. A window
+  // counts from its copy phase on.
   bool h2d_done(int64_t k);
   void wait_h2d(int64_t k);
   int copy_lanes() const { return lanes_; }
+  // A caller that will run the copy phase ahead (submit_copy, then the oldest window's results,
+  // then submit_chain) asks for the second lane where the engine left it to that: three buffers
+  // with copy_ahead() and no MISLO_COPY_LANES. Opens and warms the lane (a few ms, once: call it
+  // before the windows that matter); from the next window on window k copies on lane k & 1.
+  // Returns whether two lanes are in use; does nothing anywhere else.
+  bool take_copy_lanes();
   bool query(int64_t k);      // window k's results are in host memory
   void wait(int64_t k);
   const double* packet(int64_t k) const { return bufs_[k % nb_].packet_host; }
   ResultView results(int64_t k) const { return layout().view<const uint8_t>(bufs_[k % nb_].res_host); }
   ResultLayout layout() const { return ResultLayout{(size_t)cfg_.group_cap}; }
-  // device time of window k (ms): DMA start -> results in host memory, and the compute stream's share
+  // device time of window k (ms): DMA start -> results in host memory, and the compute stream's share.
+  // Like copy_ms, for any window whose buffer's chain has not been queued again (k > newest - nb):
+  // the copy-side marks are kept 2 nb deep, so window k + nb's copy phase does not disturb them.
   std::pair<float, float> window_ms(int64_t k);
   // window k's DMA span (first DMA's start to the last one's end: with two lanes it shares the
   // link with its neighbours' DMAs) and the time from window k - 1's last DMA to window k's first
@@ -356,12 +381,21 @@ class WindowEngine {
     uint32_t* remote_n;                   // their count
     const BufSet* set;
     const GenMeta* gen_prev;  // the previous window's: buffer b - 1's set (or this one's own)
-    // h2d_done: the window's last DMA ended (timed: it is also the end of the window's copy span)
-    hipEvent_t h2d_done, head_done, front_done, compute_done, comm_done, xchg_done;
-    hipEvent_t t_start, t_comp0, t_comp1, t_end;
+    hipEvent_t head_done, front_done, compute_done, comm_done, xchg_done;
+    hipEvent_t t_comp0, t_comp1, t_end;
     const int* counts() const { return reinterpret_cast<const int*>(in); }
   };
   std::vector<Buf> bufs_;
+  // The copy side's events of window k, in slot k % (2 nb): the copy phase of window k + nb runs
+  // while window k may still be uncollected, and window_ms(k) / copy_ms(k) need k's own records.
+  // t_start: before the window's first DMA. h2d_done: its last DMA ended (the host sleeps on it,
+  // the front stream waits for it, and it ends the window's timed copy span). A slot is recorded
+  // again by window k + 2 nb, long after the copy phase of k + nb synchronised it (CopiedUpTo).
+  struct CopyMark {
+    hipEvent_t t_start, h2d_done;
+  };
+  std::vector<CopyMark> marks_;
+  const CopyMark& mark(int64_t k) const { return marks_[copy_mark_slot(k, nb_)]; }
   hipEvent_t ev_fork_ = nullptr, ev_sigbase_ = nullptr, ev_spans_ = nullptr;
   bool branch_ = false;
   bool xspan_ = false;  // with the exchange: Stage::XchgHead, and Stage::XchgSpans on side_
@@ -371,13 +405,21 @@ class WindowEngine {
   // Copy lanes (copylanes.h): window k's three DMAs go back to back to copy_[k & 1] when there
   // are two, so one lane's DMAs are already queued on its engine while the other hands a finished
   // window over to its end marker and the next window's start marker. Two with overlapped windows
-  // and four or more buffers (MISLO_COPY_LANES=1|2 overrides where windows overlap; with three
-  // buffers two lanes did not beat one, alloc()); one with MISLO_ONE_STREAM, with the exchange
-  // sized in, and from init_comm on. The second lane is created at the highest stream priority, which draws its
+  // and four or more buffers; with three and copy_ahead(), once the caller asked for them
+  // (take_copy_lanes(): until then, and for a caller of submit() alone, one lane as before);
+  // MISLO_COPY_LANES=1|2 overrides where windows overlap (alloc()). One with MISLO_ONE_STREAM,
+  // with the exchange sized in, and from init_comm on. The second lane is created at the highest stream priority, which draws its
   // hardware queue from the other pool than copy, front and compute (MISLO_COPY_LANE_PRIO=0:
   // default priority).
   hipStream_t copy_[kMaxCopyLanes] = {nullptr, nullptr};
   int lanes_ = 1;
+  bool copy_ahead_ = false;
+  bool lane_on_request_ = false;  // three buffers, copy-ahead, no MISLO_COPY_LANES: take_copy_lanes() adds the lane
+  // submit_copy(submitted_) has run and its submit_chain has not: the window's DMAs are queued
+  // (h2d_done / wait_h2d answer for it), nothing else of it is
+  bool copy_open_ = false;
+  int copy_groups_ = 0;  // its n_groups
+  int64_t copied_windows() const { return submitted_ + (copy_open_ ? 1 : 0); }
   CopiedUpTo copied_;
   bool copied_ready(int64_t w, bool block);
   hipStream_t compute_ = nullptr, comm_stream_ = nullptr;

@@ -77,6 +77,7 @@ void to_host(const void* src, void* dst, size_t bytes, hipStream_t st) {
                      static_cast<uint4*>(dst), n16);
 }
 
+constexpr int kCopyAheadDefault = 1;  // MISLO_COPY_AHEAD where windows overlap (profiles/copy_ahead/README.md)
 constexpr unsigned kEvWait = hipEventDisableTiming | hipEventBlockingSync;  // events the host sleeps on
 // an integer environment knob, `unset` where it is not set
 int env_int(const char* name, int unset) {
@@ -211,15 +212,26 @@ void WindowEngine::alloc() {
   overlap_ = env_int("MISLO_WINDOW_OVERLAP", !one_stream) == 1 && !one_stream &&
              !(cfg_.xchg_cap > 0 && cfg_.import_cap > 0);
   if (overlap_) front_ = mk_stream();
+  // Copy ahead (engine.h, submit_copy): window k's DMAs issued before window k - nb's results
+  // are collected, behind a host wait for that window's front stage only. Overlapped windows only
+  // (front_done exists there, and every reader of the data regions is joined into front_ before
+  // it); MISLO_COPY_AHEAD=0|1 overrides the default.
+  copy_ahead_ = overlap_ && env_int("MISLO_COPY_AHEAD", kCopyAheadDefault) == 1;
   // Copy lanes (engine.h, copylanes.h): a second copy stream, windows alternating, where windows
   // overlap. A window's own DMAs stay on one stream (one window split over the two streams
-  // measured slower). Two lanes by default from four buffers on only: with three, window k's
-  // DMAs are issued once window k - 3's results are in, the lanes seldom hold a backlog, and
-  // when they do each window's copy takes longer beside its neighbour's than the three-window
-  // pipeline hides -- 0.421-0.432 ms per window with two lanes against 0.418-0.443 with one, one
-  // lane ahead in two sessions of three; with four buffers 0.399-0.403 against 0.423-0.431
-  // (profiles/copy_lanes/README.md).
-  lanes_ = overlap_ && env_int("MISLO_COPY_LANES", nb_ >= 4 ? 2 : 1) == 2 ? 2 : 1;
+  // measured slower). Two lanes pay where a lane holds a backlog, i.e. where window k's DMAs are
+  // queued a whole window before the link gets to them. With four buffers they are (the host
+  // collects window k - 3 before it stages window k + 1: 0.399-0.403 ms per window against
+  // 0.423-0.431 with one lane, profiles/copy_lanes/README.md): two lanes from the start. With
+  // three they are only for a caller that runs the copy phase ahead of that collect (0.394-0.406
+  // against the parent's 0.420-0.443 over three sessions; copying ahead on one lane, and two
+  // lanes behind the collect, both tied with the parent: profiles/copy_ahead/README.md). So an
+  // engine with three buffers starts on one lane, as every caller of submit() has it, and a
+  // caller that will copy ahead says so once with take_copy_lanes() (lane_on_request_), before
+  // its windows. MISLO_COPY_LANES=1|2 fixes the count either way.
+  const char* lanes_env = getenv("MISLO_COPY_LANES");
+  lanes_ = overlap_ && (lanes_env ? atoi(lanes_env) == 2 : nb_ >= 4) ? 2 : 1;
+  lane_on_request_ = copy_ahead_ && !lanes_env && lanes_ == 1 && nb_ >= 3;
   copy_[1] = lanes_ == 2 ? mk_stream(env_int("MISLO_COPY_LANE_PRIO", 1) != 0) : copy_[0];
   slots_ = gens_ + (overlap_ ? 1 : 0);
   {
@@ -257,13 +269,16 @@ void WindowEngine::alloc() {
     buf.packet_host = static_cast<double*>(host_block(kPacketLen * sizeof(double)));
     for (hipEvent_t* e : {&buf.head_done, &buf.compute_done, &buf.comm_done, &buf.front_done, &buf.xchg_done})
       *e = mk_event(kEvWait);
-    buf.h2d_done = mk_event(hipEventBlockingSync);  // the host sleeps on it, and it ends the copy's timed span
-    for (hipEvent_t* e : {&buf.t_start, &buf.t_comp0, &buf.t_comp1, &buf.t_end})
-      *e = mk_event(hipEventDefault);  // timing
+    for (hipEvent_t* e : {&buf.t_comp0, &buf.t_comp1, &buf.t_end}) *e = mk_event(hipEventDefault);  // timing
     buf.res_host = static_cast<uint8_t*>(host_block(lay.bytes()));
     buf.res_dev = dalloc<uint8_t>(lay.bytes(), true);
     buf.res = lay.view(buf.res_dev);
     buf.imp = cfg_.import_cap ? dalloc<SigRec>(cfg_.import_cap) : nullptr;
+  }
+  marks_.assign((size_t)copy_mark_slots(nb_), CopyMark{});
+  for (CopyMark& m : marks_) {
+    m.t_start = mk_event(hipEventDefault);
+    m.h2d_done = mk_event(hipEventBlockingSync);  // the host sleeps on it, and it ends the copy's timed span
   }
   warm_.assign(kStageSlots * nb_, false);
   // pod metadata, ring accounting, the trace id -> hash table
@@ -418,10 +433,10 @@ size_t WindowEngine::dma(const std::vector<Seg>& segs, uint8_t* dst, size_t cap,
   return off;
 }
 
-// Window w's completion event, for a window copied_ does not know copied yet: its buffer's event
-// is still its own (CopiedUpTo, copylanes.h).
+// Window w's completion event, for a window copied_ does not know copied yet: its slot's event
+// is still its own (CopiedUpTo, copylanes.h; a slot is recorded again 2 nb windows on, CopyMark).
 bool WindowEngine::copied_ready(int64_t w, bool block) {
-  const hipEvent_t ev = bufs_[w % nb_].h2d_done;
+  const hipEvent_t ev = mark(w).h2d_done;
   if (block) {
     HIPCHECK(hipEventSynchronize(ev));
     return true;
@@ -433,12 +448,12 @@ bool WindowEngine::copied_ready(int64_t w, bool block) {
 }
 
 bool WindowEngine::h2d_done(int64_t k) {
-  if (k < 0 || k >= submitted_) return false;  // not queued: nothing of it has been copied
+  if (k < 0 || k >= copied_windows()) return false;  // not queued: nothing of it has been copied
   return copied_.done(k, lanes_, [this](int64_t w) { return copied_ready(w, false); });
 }
 
 void WindowEngine::wait_h2d(int64_t k) {
-  if (k < 0 || k >= submitted_) throw std::invalid_argument("wait_h2d: the window has not been submitted");
+  if (k < 0 || k >= copied_windows()) throw std::invalid_argument("wait_h2d: the window has not been submitted");
   copied_.done(k, lanes_, [this](int64_t w) { return copied_ready(w, true); });
 }
 
@@ -641,9 +656,52 @@ void WindowEngine::refit(const double* add) {
                   p0_ + kSlots * 16, cfg_.cap_dom, cfg_.lik_ceil);
 }
 
+// The second lane for a caller that copies ahead (alloc()): created here, so an engine that never
+// copies ahead keeps its hardware queue and memory. The first large DMA that runs while the other
+// lane's is still in flight goes to a DMA engine the process has not used yet, and setting that up
+// blocks the issuing thread for ~6 ms once (profiles/copy_lanes/README.md: "the second lane's
+// first large DMA"; a warm-up copy on the idle lane alone did not absorb it,
+// profiles/copy_ahead/README.md). A lane used from the engine's first windows pays that in the
+// caller's warm-up; this lane would pay it in the first window copied ahead, so it pays here:
+// window-sized copies into scratch on both lanes at once. Windows before this call all ran on
+// lane 0 in order, so "copied up to k" keeps following from windows k and k - 1
+// (tests/native/copyahead_host_check.cpp).
+bool WindowEngine::take_copy_lanes() {
+  if (!lane_on_request_ || copy_open_) return lanes_ == 2;
+  lane_on_request_ = false;
+  HIPCHECK(hipSetDevice(cfg_.device));
+  const hipStream_t lane = mk_stream(env_int("MISLO_COPY_LANE_PRIO", 1) != 0);
+  const size_t n = std::min<size_t>(in_bytes_ - off_kern_, size_t(64) << 20);
+  void *h = nullptr, *d = nullptr;
+  hipError_t e = hipHostMalloc(&h, 2 * n, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMalloc(&d, 2 * n);
+  if (e == hipSuccess) {
+    std::memset(h, 0, 2 * n);
+    uint8_t *hp = static_cast<uint8_t*>(h), *dp = static_cast<uint8_t*>(d);
+    for (int round = 0; round < 2 && e == hipSuccess; ++round) {
+      e = hipMemcpyAsync(dp, hp, n, hipMemcpyHostToDevice, copy_[0]);
+      if (e == hipSuccess) e = hipMemcpyAsync(dp + n, hp + n, n, hipMemcpyHostToDevice, lane);
+    }
+    const hipError_t e0 = hipStreamSynchronize(copy_[0]), e1 = hipStreamSynchronize(lane);
+    if (e == hipSuccess) e = e0 != hipSuccess ? e0 : e1;
+  }
+  if (d) (void)hipFree(d);
+  if (h) (void)hipHostFree(h);
+  HIPCHECK(e);
+  copy_[1] = lane;
+  lanes_ = 2;
+  return true;
+}
+
 void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bool learn) {
+  submit_copy(k, in);
+  submit_chain(k, in.n_groups, with_labels, learn);
+}
+
+void WindowEngine::submit_copy(int64_t k, const WindowInput& in) {
   Lap whole;
   if (k != submitted_) throw std::invalid_argument("windows must be submitted in order");
+  if (copy_open_) throw std::logic_error("submit_copy: the window's chain phase has not been queued");
   const int n_groups = in.n_groups;
   if (n_groups < 0 || n_groups > cfg_.group_cap) throw std::invalid_argument("n_groups exceeds group capacity");
   size_t kb = 0, ub = 0, sb = 0;
@@ -659,15 +717,22 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   if (n_k + n_u > (size_t)cfg_.sig_cap || n_u > (size_t)cfg_.user_cap || n_s > (size_t)cfg_.span_cap)
     throw std::invalid_argument("window exceeds the engine's capacity (events / user records / spans)");
   Buf& buf = bufs_[k % nb_];
-  // host back-pressure: at most max_ahead windows queued beyond the one computing
+  const CopyMark& mk = mark(k);
+  // host back-pressure: at most max_ahead windows queued beyond the one computing. Copying ahead
+  // leaves it to the chain phase: the DMAs below collide with the front stage of window k - nb only
   Lap phase;
-  if (k >= max_ahead_) HIPCHECK(hipEventSynchronize(bufs_[(k - max_ahead_) % nb_].compute_done));
+  if (!copy_ahead_ && k >= max_ahead_) HIPCHECK(hipEventSynchronize(bufs_[(k - max_ahead_) % nb_].compute_done));
   // the pinned head / staging of the buffer were last read by the DMAs of window k - nb (on
-  // whichever lane they ran: the event is the buffer's), which also wrote the device block last
+  // whichever lane they ran) and by its head load; those DMAs also wrote the device block last
   if (k >= nb_) {
-    HIPCHECK(hipEventSynchronize(buf.h2d_done));
-    copied_.reused(k, nb_);  // before the event is recorded again below
+    HIPCHECK(hipEventSynchronize(mark(k - nb_).h2d_done));
+    copied_.reused(k, nb_);  // every window <= k - nb has been copied (their slots are re-recorded later still)
     HIPCHECK(hipEventSynchronize(buf.head_done));
+    // the data regions of the device block (ring bytes, user records, spans) are read by the
+    // front stage alone -- definitions, decode, span decode; a span branch is joined into front_
+    // before the event -- and the back stage reads the head only, which the head load writes on
+    // front_ behind its own wait for the back stage of window k - 2
+    if (copy_ahead_) HIPCHECK(hipEventSynchronize(buf.front_done));
   }
   phase(wait_us_);
   int32_t* c = reinterpret_cast<int32_t*>(buf.head_host);
@@ -688,13 +753,14 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   for (int g = 0; g < cfg_.group_cap; ++g) lab[g] = (in.labels && g < n_groups) ? in.labels[g] : -1;
   // The window's DMAs: the BPF ring's bytes, the user-space records and the spans, back to back
   // on the window's copy lane between one start marker and one completion event; the head is
-  // loaded on the compute stream (below). The copy stream waits for nothing on the device: the
-  // device block's previous reader, window k - nb, has computed, because the host waited above
-  // for compute_done of window k - max_ahead_, max_ahead_ <= nb_ (constructor) and every stage
-  // that reads the block (front_, side_) is joined into the in-order compute stream before that
-  // event. A wait on the copy stream costs a queue hand-off with the link idle.
+  // loaded on the compute stream (submit_chain). The copy stream waits for nothing on the device:
+  // the regions' previous reader, window k - nb, is through with them, because the host waited
+  // above -- for its front_done when copying ahead, else for compute_done of window
+  // k - max_ahead_, max_ahead_ <= nb_ (constructor), and every stage that reads the block (front_,
+  // side_) is joined into the in-order compute stream before that event. A wait on the copy
+  // stream costs a queue hand-off with the link idle.
   const hipStream_t cs = copy_[copy_lane(k, lanes_)];
-  HIPCHECK(hipEventRecord(buf.t_start, cs));
+  HIPCHECK(hipEventRecord(mk.t_start, cs));
   size_t st_off = 0;
   Lap part;  // DMA issue: ring bytes, head (nothing: not on the copy stream), user records, spans
   dma(in.kernel, buf.in + off_kern_, kern_bytes(), buf.staging, st_off, cs);
@@ -704,13 +770,28 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   part(split_us_[2]);
   dma(in.spans, buf.in + off_span_, 64 * (size_t)cfg_.span_cap, buf.staging, st_off, cs);
   part(split_us_[3]);
-  HIPCHECK(hipEventRecord(buf.h2d_done, cs));
+  HIPCHECK(hipEventRecord(mk.h2d_done, cs));
   phase(dma_us_);
+  copy_open_ = true;
+  copy_groups_ = n_groups;
+  whole(issue_us_);
+}
+
+void WindowEngine::submit_chain(int64_t k, int n_groups, bool with_labels, bool learn) {
+  Lap whole;
+  if (!copy_open_ || k != submitted_) throw std::logic_error("submit_chain: not the window submit_copy queued last");
+  if (n_groups != copy_groups_) throw std::invalid_argument("submit_chain: n_groups differs from the copy phase's");
+  Buf& buf = bufs_[k % nb_];
+  const CopyMark& mk = mark(k);
+  Lap phase;
+  // host back-pressure (see submit_copy, which waited already unless it copied ahead)
+  if (copy_ahead_ && k >= max_ahead_) HIPCHECK(hipEventSynchronize(bufs_[(k - max_ahead_) % nb_].compute_done));
+  phase(wait_us_);
   // the stream of the window's head and front half: front_ with overlapped windows (never with
   // the exchange: overlap_ is off for an engine sized for it or holding a communicator). It waits
   // for this window's own DMAs only, whatever the other lane is doing.
   hipStream_t fs = overlap_ ? front_ : compute_;
-  HIPCHECK(hipStreamWaitEvent(fs, buf.h2d_done, 0));
+  HIPCHECK(hipStreamWaitEvent(fs, mk.h2d_done, 0));
   // overlapped: the front stage of window k starts once the back stage of window k - 2 ended. It
   // overwrites the generation slot that stage probed as its oldest, and (two buffers) the buffer
   // set and the head that stage read; with it at most one window's back stage runs beside a front.
@@ -808,6 +889,7 @@ void WindowEngine::submit(int64_t k, const WindowInput& in, bool with_labels, bo
   HIPCHECK(hipEventRecord(buf.t_end, comm_stream_));
   HIPCHECK(hipEventRecord(buf.comm_done, comm_stream_));
   ++submitted_;
+  copy_open_ = false;
   phase(tail_us_);
   whole(issue_us_);
   ++issue_n_;
@@ -835,11 +917,11 @@ std::vector<float> WindowEngine::copy_ms(int64_t k) {
   // the copy's duration and the copy stream's idle time before it. Two lanes: windows k-1 and k
   // copy side by side and share the link, so the span is longer than the bytes alone would take
   // and the second value is negative where they overlap.
-  const Buf& buf = bufs_[k % nb_];
+  const CopyMark& mk = mark(k);
   float dur = 0.f, gap = -1.f;
-  HIPCHECK(hipEventSynchronize(buf.h2d_done));
-  HIPCHECK(hipEventElapsedTime(&dur, buf.t_start, buf.h2d_done));
-  if (k >= 1 && nb_ > 1) HIPCHECK(hipEventElapsedTime(&gap, bufs_[(k - 1) % nb_].h2d_done, buf.t_start));
+  HIPCHECK(hipEventSynchronize(mk.h2d_done));
+  HIPCHECK(hipEventElapsedTime(&dur, mk.t_start, mk.h2d_done));
+  if (k >= 1) HIPCHECK(hipEventElapsedTime(&gap, mark(k - 1).h2d_done, mk.t_start));
   return {dur, gap};
 }
 
@@ -847,7 +929,7 @@ std::pair<float, float> WindowEngine::window_ms(int64_t k) {
   const Buf& buf = bufs_[k % nb_];
   float total = 0.f, comp = 0.f;
   HIPCHECK(hipEventSynchronize(buf.t_end));
-  HIPCHECK(hipEventElapsedTime(&total, buf.t_start, buf.t_end));
+  HIPCHECK(hipEventElapsedTime(&total, mark(k).t_start, buf.t_end));
   HIPCHECK(hipEventElapsedTime(&comp, buf.t_comp0, buf.t_comp1));
   return {total, comp};
 }
@@ -986,11 +1068,12 @@ void WindowEngine::init_comm(const ncclUniqueId& id, int rank, int world) {
   // world 1 is a real communicator too: every collective of the window chain runs (on one rank),
   // which is how a one-GPU box exercises the multi-GPU path (tests/test_rccl_single.py)
   if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("communicator rank / world");
-  if (submitted_) throw std::logic_error("init_comm before the first window");
+  if (submitted_ || copy_open_) throw std::logic_error("init_comm before the first window");
   HIPCHECK(hipSetDevice(cfg_.device));
   if (overlap_) {  // the windows of an engine with a communicator run the serial chain on compute_
     HIPCHECK(hipStreamSynchronize(front_));  // a pod table upload queued there
     overlap_ = false;
+    copy_ahead_ = lane_on_request_ = false;
     lanes_ = 1;  // no window has been submitted: lane 1 stays idle
     // the serial chain's default again: the span side on its own stream
     if (!getenv("MISLO_SPAN_STREAM")) enable_span_branch();

@@ -161,6 +161,7 @@ class CpuRingEngine:
 
         self.sig_cap, self.span_cap, self.group_cap, self.user_cap = sig_cap, span_cap, group_cap, user_cap
         self.buffers = int(n_buffers)
+        self.copy_ahead = False  # a window is evaluated inside submit: no copy phase to issue early
         self.window_ms_, self.threshold, self.fanout, self.group_mode = window_ms, threshold, fanout, group_mode
         self.n_dom, self.ttft_slo_ms = n_dom, float(ttft_slo_ms)
         self.shard_rank, self.shard_world = int(shard_rank), int(shard_world)

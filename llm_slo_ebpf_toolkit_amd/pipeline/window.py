@@ -322,6 +322,46 @@ class WindowPipeline:
             self._host_refit(k - 2)  # window k-2 is done or nearly (k-1 would stall the host)
         return k
 
+    @property
+    def copy_ahead(self) -> bool:
+        """The two-phase pair below may issue window k's DMAs before window k - nb is collected: the
+        engine offers it (ops/csrc/engine.h ``copy_ahead``: overlapped windows on one GPU) and no side
+        tracker is configured -- their steps are queued with the window and read with its results,
+        so they keep ``submit``'s order."""
+        return bool(getattr(self.eng, "copy_ahead", False)) and all(
+            t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset))
+
+    def prepare_copy_ahead(self) -> bool:
+        """For the caller that will stage windows in two halves (agent/worker.py): where
+        ``copy_ahead`` holds, ask the engine for the second copy lane it leaves to such a caller
+        (three buffers; ops/csrc/engine.h ``take_copy_lanes``). Costs a few ms once, so it belongs
+        before the windows that matter. Returns ``copy_ahead``."""
+        if not self.copy_ahead:
+            return False
+        self.eng.take_copy_lanes()
+        return True
+
+    def submit_copy(self, kernel, user, spans, n_groups: int, labels=None, bases=(0, 0, 0, 0),
+                    user_rec: int = 64) -> int:
+        """The copy phase of the next window (``submit``'s arguments): its DMAs are queued, window
+        k - nb's packet and results stay readable until ``submit_chain``. Returns its index."""
+        if user_rec in (16, 24) and not any(int(b) for b in bases) and any(int(n) for _, n in user):
+            raise ValueError("USER24 records need the window's epoch bases (all are 0)")
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.int32)
+        self.eng.submit_copy(self.k, list(kernel), list(user), list(spans), int(n_groups), lab,
+                             [int(b) for b in bases], int(user_rec))
+        return self.k
+
+    def submit_chain(self, n_groups: int, with_labels: bool = True, learn: Optional[bool] = None) -> int:
+        """The chain phase of the window ``submit_copy`` queued: everything else of ``submit``."""
+        k = self.k
+        learn = (self.learn and with_labels) if learn is None else learn
+        self.eng.submit_chain(k, int(n_groups), bool(with_labels), bool(learn))
+        self.k += 1
+        if self.learn and not self.device_refit and k >= 2:
+            self._host_refit(k - 2)
+        return k
+
     def _host_refit(self, j: int) -> None:
         """LDA (or host-refit Bayes): fold window j's all-reduced statistics on the host."""
         self.eng.wait(j)
@@ -682,6 +722,8 @@ class RingWindowSource:
         self.carried = 0   # records past a window's budget, summed over windows (should stay 0)
         self.reap_s = self.submit_s = 0.0  # host time: waiting for / reading back finished windows, submitting
         self.prev_cut_ns = 0  # the last timed cut (the open-request tracker's previous cut)
+        self.staged: Optional[list] = None  # a pending entry between stage_copy and stage_chain
+        self._staged_groups = 0             # its incident groups
 
     def publish_epoch(self, now_ns: Optional[int] = None) -> int:
         v = self.clock.publish(int(now_ns if now_ns is not None else time.time_ns()))
@@ -728,7 +770,8 @@ class RingWindowSource:
             # ring space is free up to the decoded records, short of the first range still needed:
             # a late range, or one a window in flight holds (a re-submitted range lies behind
             # ranges already decoded)
-            hold = min([p for p, _, _ in self.late] + [p for e in self.pending for p, _, _ in e[1]], default=None)
+            held = self.pending + ([self.staged] if self.staged is not None else [])  # + the one between its halves
+            hold = min([p for p, _, _ in self.late] + [p for e in held for p, _, _ in e[1]], default=None)
             self.kernel_done = max(self.kernel_done, min(hold, self.kernel_seen) if hold is not None else self.kernel_seen)
             if not self.shared:
                 self.ring.set_consumer_pos(max(self.ring.consumer_pos, self.kernel_done))
@@ -772,14 +815,11 @@ class RingWindowSource:
             left -= take
         return out, n
 
-    def stage(self, cut: Cut, n_groups: int, labels: Optional[np.ndarray] = None, with_labels: Optional[bool] = None,
-              learn: Optional[bool] = None) -> Dict[str, int]:
-        """Submit the window up to ``cut``; returns what went in."""
-        t0 = time.perf_counter()
+    def _take(self, cut: Cut):
+        """The next window's share of the rings up to ``cut``, taken (the read positions move): the
+        kernel ranges [(pos, batch records, window)] with their DMA segments and rows -- late ranges
+        first --, the user records' and the spans' segments and counts."""
         pipe = self.pipe
-        self.reap(keep=pipe.nb - 1)
-        t1 = time.perf_counter()
-        self.reap_s += t1 - t0
         budget = pipe.sig_cap
         k_ranges, kern = [], []
         n_k = 0
@@ -823,6 +863,17 @@ class RingWindowSource:
                                            pipe.span_cap)
             self.carried += max(0, cut.spans - self.spos) - n_s
             self.spos += n_s
+        return k_ranges, kern, n_k, user, n_u, spans, n_s
+
+    def stage(self, cut: Cut, n_groups: int, labels: Optional[np.ndarray] = None, with_labels: Optional[bool] = None,
+              learn: Optional[bool] = None) -> Dict[str, int]:
+        """Submit the window up to ``cut``; returns what went in."""
+        t0 = time.perf_counter()
+        pipe = self.pipe
+        self.reap(keep=pipe.nb - 1)
+        t1 = time.perf_counter()
+        self.reap_s += t1 - t0
+        k_ranges, kern, n_k, user, n_u, spans, n_s = self._take(cut)
         wl = labels is not None if with_labels is None else with_labels
         if pipe.tracker is not None:  # the open requests see the window's spans and the cut's time
             pipe.track_open(spans, cut.t_ns, self.prev_cut_ns, n_groups)
@@ -844,6 +895,56 @@ class RingWindowSource:
         self.host_s += time.perf_counter() - t0
         self.n += 1
         self.last = {"k": k, "n_kernel": n_k, "n_user": n_u, "n_spans": n_s, "n_events": n_k + n_u}
+        return self.last
+
+    def stage_copy(self, cut: Cut, n_groups: int, labels: Optional[np.ndarray] = None) -> int:
+        """The first half of ``stage`` where the pipeline offers ``copy_ahead``: take the window up to
+        ``cut`` and queue its DMAs, without waiting for any earlier window -- the reap before it
+        only takes what is finished. The caller then reads the oldest window's results and calls
+        ``stage_chain``; until then the window is held in ``staged``, so none of its ring ranges is
+        freed between the halves. Returns the window's index.
+
+        Late (busy) ranges: a range that a window still running here reports busy is found by
+        ``stage_chain``'s reap or the next call's, one window later than ``stage`` finds it. Flat out
+        at three buffers such a range is then three windows old, as it already is with ``stage``, and
+        is dropped and counted in ``late_dropped``; at the agent's window period every earlier
+        window has finished at the cut and both orders find it at the same window."""
+        if not self.pipe.copy_ahead:
+            raise RuntimeError("stage_copy needs a pipeline with copy_ahead (use stage)")
+        if self.staged is not None:
+            raise RuntimeError("stage_copy: the previous window's stage_chain has not run")
+        t0 = time.perf_counter()
+        pipe = self.pipe
+        self.reap()
+        t1 = time.perf_counter()
+        self.reap_s += t1 - t0
+        k_ranges, kern, n_k, user, n_u, spans, n_s = self._take(cut)
+        t2 = time.perf_counter()
+        k = pipe.submit_copy(kern, user, spans, n_groups, labels, cut.bases, user_rec=self.user_rec)
+        self.submit_s += time.perf_counter() - t2
+        self.staged = [k, k_ranges, n_u, n_s, False]
+        self.last = {"k": k, "n_kernel": n_k, "n_user": n_u, "n_spans": n_s, "n_events": n_k + n_u}
+        self._staged_groups = n_groups
+        self.host_s += time.perf_counter() - t0
+        return k
+
+    def stage_chain(self, with_labels: bool = True, learn: Optional[bool] = None) -> Dict[str, int]:
+        """The second half: ``stage``'s reap (at most nb - 1 windows outstanding: window k - nb's
+        packet is read before this window's chain overwrites it), the chain phase, and only then
+        the window enters ``pending``. Returns what went in, like ``stage``."""
+        if self.staged is None:
+            raise RuntimeError("stage_chain without stage_copy")
+        t0 = time.perf_counter()
+        pipe = self.pipe
+        self.reap(keep=pipe.nb - 1)
+        t1 = time.perf_counter()
+        self.reap_s += t1 - t0
+        pipe.submit_chain(self._staged_groups, with_labels=with_labels, learn=learn)
+        self.submit_s += time.perf_counter() - t1
+        self.pending.append(self.staged)
+        self.staged = None
+        self.host_s += time.perf_counter() - t0
+        self.n += 1
         return self.last
 
     def step(self, n_groups: int, labels=None, cut: Optional[Cut] = None, with_labels: Optional[bool] = None) -> int:
