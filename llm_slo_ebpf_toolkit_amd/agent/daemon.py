@@ -234,6 +234,13 @@ class AgentOptions:
     onset_bins: int = 1024               # bins of the ring per service (a power of two in 64..8192)
     onset_ref_burn: float = 2.0          # the CUSUM's reference breach rate, in error-budget multiples (untuned)
     onset_alarm_breaches: int = 3        # excess breaches over the reference rate that count as an alarm (untuned)
+    # per service, the time per output token the finished requests' spans carry (the decode-phase SLI): its
+    # distribution and the requests by (TTFT breach, TPOT breach), of the window and of a rolling horizon, on the
+    # GPU (pipeline/decodesli.py): a decode field in the decision log and four series; one GPU; nothing is
+    # checkpointed
+    decode_sli: bool = False
+    tpot_slo_ms: float = 100.0           # the TPOT SLO (reasoned, not measured, untuned: 10 tokens/s)
+    decode_horizon_windows: int = 0      # windows of the rolling horizon (0: the TTFT sketch's)
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -759,6 +766,8 @@ class Agent:
                        and g < len(res["pod_rec_top"]) else {}),
                     **({"onset": self._onset_entry(res, g, t_ns)} if res.get("onset_rows") is not None
                        and g < len(res["onset_rows"]) else {}),
+                    **({"decode": self._decode_entry(res, g)} if res.get("decode_cells") is not None
+                       and g < len(res["decode_cells"]) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
                                                    ("no_burn" if not burning else "recovered"))}) + "\n")
             if not confident:
@@ -844,6 +853,20 @@ class Agent:
                 "excess": round(int(r["s_now"]) * 1e-6, 6), "requests": int(r["n_exc"]), "breaches": int(r["b_exc"]),
                 "clipped": bool(int(r["flags"]) & CLIPPED)}
 
+    def decode_horizon(self) -> int:
+        """Windows of the decode SLI's rolling horizon: the flag, or the TTFT sketch's."""
+        w = int(self.o.decode_horizon_windows)
+        return w if w > 0 else self.ttft_horizon()
+
+    @staticmethod
+    def _decode_entry(res: dict, g: int) -> dict:
+        """Group g's decode SLI for the decision log: the window's requests by (TTFT breach, TPOT breach), its
+        goodput and its TPOT quantiles and mean, and the same over the horizon; ``None`` without a request."""
+        from ..pipeline.decodesli import summary
+
+        return {**summary(res["decode_cells"][g], res["decode_sum_ms"][g], res["decode_q"][g]),
+                "horizon": summary(res["decode_cells_roll"][g], res["decode_sum_ms_roll"][g], res["decode_q_roll"][g])}
+
     def _exemplar_ids(self, res: dict, g: int) -> dict:
         """``request_ids`` (span ids) and ``trace_ids`` (de-duplicated, order kept) of group g's recent
         exemplars beyond the TTFT SLO; nothing when none is, or the tracker is off."""
@@ -918,7 +941,9 @@ class Agent:
             self.metrics.observe_pods(res, head["pod_breakdown"], names)
         if head.get("breach_onset") is not None and res.get("onset_rows") is not None:
             self.metrics.observe_onset(res, head["breach_onset"], names, t_ns, self.onset_bin_ns())
-        attrs = self._attributions(G, names, res, t_ns, model)
+        if head.get("decode_sli") is not None and res.get("decode_cells") is not None:
+            self.metrics.observe_decode(res, head["decode_sli"], names)
+        attrs =self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
             self.writers.emit_attribution(attr)
@@ -1038,6 +1063,9 @@ class Agent:
         if o.breach_onset and N > 1:
             raise ValueError("--breach-onset runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the breach-onset tracker's are read on the host")
+        if o.decode_sli and N > 1:
+            raise ValueError("--decode-sli runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the decode SLI tracker's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1089,7 +1117,8 @@ class Agent:
                             pod_pairs=int(o.pod_pairs),
                             breach_onset=int(o.onset_bins) if o.breach_onset else 0,
                             onset_bin_ns=self.onset_bin_ns(), onset_ref_ppm=self.onset_ref_ppm(),
-                            onset_alarm=int(o.onset_alarm_breaches))
+                            onset_alarm=int(o.onset_alarm_breaches),
+                            decode_sli=self.decode_horizon() if o.decode_sli else 0, tpot_slo_ms=float(o.tpot_slo_ms))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):
@@ -1125,7 +1154,8 @@ class Agent:
                         ipcache["m"] = _procfs.pod_addresses(_procfs.pod_processes())
                         ipcache["t"] = time.monotonic()
                     return ipcache["m"]
-            mapper = SpanMapper(groups, self.pod_ids.id, node_id, pod_ips=pod_ips, forwarders=o.otlp_forwarders)
+            mapper = SpanMapper(groups, self.pod_ids.id, node_id, pod_ips=pod_ips, forwarders=o.otlp_forwarders,
+                                decode_sli=bool(o.decode_sli))
             mapper.slo_ms = float(o.ttft_slo_ms)
             mapper.keep_trace_high = bool(o.request_exemplars)  # exemplars quote the whole W3C trace id
             self.mapper = mapper

@@ -152,6 +152,21 @@ class AgentMetrics:
                                       "out_of_group (an SLI record of a group beyond the window's), no_time (no start "
                                       "time, in no bin), future (a start time past the cut, placed in the newest bin), "
                                       "too_old (a start time before the ring, placed nowhere).", ("reason",))
+        # decode SLI (agent --decode-sli, pipeline/decodesli.py): time per output token and goodput
+        self.tpot_quantile = r.gauge("llm_slo_agent_tpot_ms",
+                                     "Time per output token quantile (ms) by service over the last "
+                                     "--decode-horizon-windows windows, from the histogram on the GPU (16 buckets per "
+                                     "octave: within 1/32 of the nearest-rank value).", ("service", "quantile"))
+        self.goodput = r.gauge("llm_slo_agent_goodput_ratio",
+                               "Share of the service's finished requests over the last --decode-horizon-windows windows "
+                               "that met both the TTFT and the TPOT SLO.", ("service",))
+        self.decode_requests = r.counter("llm_slo_agent_decode_requests_total",
+                                         "Finished requests with a TPOT, by service and outcome: good (both SLOs met), "
+                                         "ttft_only / tpot_only (that SLO breached alone), both.", ("service", "outcome"))
+        self.decode_events = r.counter("llm_slo_agent_decode_events_total",
+                                       "Decode SLI events: invalid (a TPOT with a NaN or negative TTFT), out_of_group (a "
+                                       "group beyond the window's), no_decode (a finished request without a TPOT).",
+                                       ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -330,6 +345,25 @@ class AgentMetrics:
             self.onset_state.set(float(state), name)
         for reason in EVENT_STATS:
             self.onset_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_decode(self, res: dict, stats: dict, names) -> None:
+        """One window of the decode SLI tracker: ``res`` carries the decode_* arrays per group
+        (pipeline/decodesli.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.decodesli import CELLS, EVENT_STATS, QUANTILE_NAMES
+
+        roll = np.asarray(res["decode_cells_roll"], dtype=np.int64)
+        for g, cells in enumerate(np.asarray(res["decode_cells"], dtype=np.int64).tolist()):
+            name = names[g] if g < len(names) else f"group-{g}"
+            for outcome, n in zip(CELLS, cells):
+                if n:
+                    self.decode_requests.inc(float(n), name, outcome)
+            n_roll = int(roll[g].sum())
+            if n_roll:  # an empty horizon keeps its last values: NaN would break rate() and min()
+                self.goodput.set(float(roll[g, 0]) / n_roll, name)
+                for q, v in zip(QUANTILE_NAMES, np.asarray(res["decode_q_roll"][g], dtype=np.float64).tolist()):
+                    self.tpot_quantile.set(v, name, q)
+        for reason in EVENT_STATS:
+            self.decode_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

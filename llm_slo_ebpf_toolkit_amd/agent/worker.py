@@ -91,10 +91,14 @@ class WorkerSpec:
     onset_bin_ns: int = 125_000_000  # a bin's length (agent --onset-bin-ms)
     onset_ref_ppm: int = 20000  # the CUSUM's reference breach rate, millionths (agent --onset-ref-burn)
     onset_alarm: int = 3        # excess breaches that count as an alarm (agent --onset-alarm-breaches)
+    decode_sli: int = 0         # windows of the decode SLI's rolling horizon (agent --decode-sli); 0: off
+    tpot_slo_ms: float = 100.0  # the TPOT SLO (agent --tpot-slo-ms)
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
 POD_RESULT_KEYS = tuple(f"pod_{s}_{f}" for s in ("win", "rec") for f in ("n", "b", "pods", "pods_b", "k_top", "top"))
+# the decode SLI's (pipeline/decodesli.py RESULT_KEYS)
+DECODE_RESULT_KEYS = ("decode_cells", "decode_cells_roll", "decode_sum_ms", "decode_sum_ms_roll", "decode_q", "decode_q_roll")
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -109,7 +113,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
-                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows"):
+                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -183,7 +187,8 @@ class WorkerCore:
                                    pod_breakdown=spec.pod_breakdown, pod_windows=spec.pod_windows,
                                    pod_pairs=spec.pod_pairs, breach_onset=spec.breach_onset,
                                    onset_bin_ns=spec.onset_bin_ns, onset_ref_ppm=spec.onset_ref_ppm,
-                                   onset_alarm=spec.onset_alarm)
+                                   onset_alarm=spec.onset_alarm, decode_sli=spec.decode_sli,
+                                   tpot_slo_ms=spec.tpot_slo_ms)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -357,6 +362,10 @@ class WorkerCore:
                 from ..pipeline.onset import stats_dict as onset_stats
 
                 d["breach_onset"] = onset_stats(pipe.onset_results(k, n_groups)["stats"])
+            if pipe.decode is not None:  # the decode SLI tracker's statistics of the window
+                from ..pipeline.decodesli import stats_dict as decode_stats
+
+                d["decode_sli"] = decode_stats(pipe.decode_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

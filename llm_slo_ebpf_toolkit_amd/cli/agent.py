@@ -146,6 +146,16 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         ("onset-alarm-breaches", d.onset_alarm_breaches, "--breach-onset: excess breaches over the reference rate "
                                                          "that count as an alarm (untuned: one slow request cannot "
                                                          "reach 3)"),
+        ("decode-sli", False, "gpu engine: per service, the time per output token (TPOT) the finished requests' spans "
+                              "carry (llm.slo.tpot_ms, else from llm.slo.tokens_per_sec or the output token count) -- "
+                              "its distribution and the requests by (TTFT breach, TPOT breach) of the window and of a "
+                              "rolling horizon, on the GPU -- a decode field in the decision log, "
+                              "llm_slo_agent_tpot_ms / _goodput_ratio / _decode_requests_total{service}; one GPU only; "
+                              "the horizon is not checkpointed"),
+        ("tpot-slo-ms", d.tpot_slo_ms, "--decode-sli: the TPOT SLO, ms per output token (reasoned, not measured, "
+                                       "untuned: 10 tokens/s is about the slowest stream a reader does not outpace)"),
+        ("decode-horizon-windows", d.decode_horizon_windows, "--decode-sli: windows of the rolling horizon (0 = "
+                                                             "--ttft-horizon-windows' value)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -201,6 +211,8 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         pod_pairs=int(a.pod_pairs),
         breach_onset=bool(a.breach_onset), onset_bin_ms=float(a.onset_bin_ms), onset_bins=int(a.onset_bins),
         onset_ref_burn=float(a.onset_ref_burn), onset_alarm_breaches=int(a.onset_alarm_breaches),
+        decode_sli=bool(a.decode_sli), tpot_slo_ms=float(a.tpot_slo_ms),
+        decode_horizon_windows=int(a.decode_horizon_windows),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

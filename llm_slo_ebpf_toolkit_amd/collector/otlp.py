@@ -301,16 +301,40 @@ def _truthy(v: object) -> bool:
     return v is True or (isinstance(v, str) and v.lower() == "true") or (isinstance(v, (int, float)) and v == 1)
 
 
+def tpot_us(attrs: Dict[str, object], ttft_ms: float, latency_ms: float) -> int:
+    """A request span's time per output token in the record's integer microseconds (0: none), from
+    the first that applies: ``llm.slo.tpot_ms``; ``llm.slo.tokens_per_sec`` = r > 0 as 1000 / r;
+    ``gen_ai.usage.output_tokens`` = n >= 2 as (latency - TTFT) / (n - 1)."""
+    try:
+        v = attrs.get(semconv.ATTR_SLO_TPOT_MS)
+        if v is not None:
+            return records.tpot_us_of_ms(float(v))
+        r = attrs.get(semconv.ATTR_SLO_TOKENS_PER_SEC)
+        if r is not None:
+            r = float(r)
+            return records.tpot_us_of_ms(1000.0 / r) if r > 0.0 else 0
+        n = attrs.get("gen_ai.usage.output_tokens")
+        if n is not None and float(n) >= 2:
+            return records.tpot_us_of_ms((float(latency_ms) - float(ttft_ms)) / (float(n) - 1.0))
+    except (TypeError, ValueError):
+        pass
+    return 0
+
+
 class SpanMapper:
     """OTLP spans -> SPAN records on the agent's ids."""
 
     def __init__(self, groups: GroupTable, pod_id: Callable[[str], int], node_id: int = 0,
-                 pod_ips: Optional[Callable[[], Dict[str, set]]] = None, forwarders: str = ""):
+                 pod_ips: Optional[Callable[[], Dict[str, set]]] = None, forwarders: str = "",
+                 decode_sli: bool = False):
         """``pod_ips()`` -> {IP: pod uids at that IP} of this node's pods (procfs.pod_addresses):
         a span that names a pod is kept only when it comes from that pod's address (or from an
         address the map does not know). ``forwarders``: CIDRs of trusted span forwarders (an
-        OpenTelemetry collector relaying many pods' spans) the address check does not apply to."""
+        OpenTelemetry collector relaying many pods' spans) the address check does not apply to.
+        ``decode_sli``: a request span's time per output token goes into bits 8-31 of its ``flags``
+        (``tpot_us``); off, the records are what they were."""
         self.groups, self.pod_id, self.node_id = groups, pod_id, node_id
+        self.decode_sli = bool(decode_sli)
         self.pod_ips = pod_ips
         self.forwarders = [ipaddress.ip_network(c.strip(), strict=False) for c in forwarders.split(",") if c.strip()]
         self.conflicts = 0  # spans that named a pod already bound to another service (dropped)
@@ -473,6 +497,10 @@ class SpanMapper:
                             self._final[th] = True
                             while len(self._final) > self.retrieval_cap:
                                 self._final.popitem(last=False)
+            # the decode SLI rides on the request span: the record that ends the request, not its start
+            # or first-token record (one without a trace id carries no flag, but is no request span either)
+            if self.decode_sli and not start and v is not None and not _truthy(a.get(semconv.ATTR_SLO_TTFT_EARLY)):
+                fl |= records.pack_tpot_us(tpot_us(a, float(v), (t1 - t0) / 1e6))
             flags.append(fl)
             # the trace's retrieval breakdown goes to its first record (a first-token record when the
             # service exports one), once: later records of the trace carry only what arrives with them

@@ -235,12 +235,47 @@ SPAN = np.dtype([
     # request span (its keys but the connection: the request span brings the pod+conn tier), so the
     # request's kernel evidence reaches the window its SLI is counted in; bit 3 (SPAN_START): a start
     # record (llm.slo.request_start: "this request started at ts_ns", ttft_ms NaN, always with
-    # SPAN_NO_SLI) -- joins, never counts; the open-request tracker (pipeline/openreq.py) reads it
+    # SPAN_NO_SLI) -- joins, never counts; the open-request tracker (pipeline/openreq.py) reads it;
+    # bits 4-7 free; bits 8-31 (SPAN_TPOT_SHIFT): the request's time per output token in integer
+    # microseconds, 0 = no decode SLI (collector/otlp.py decode_sli; pipeline/decodesli.py reads it).
+    # Every other reader tests the flag bits by mask
     ("flags", "<u4"),
 ])
 SPAN_LATE, SPAN_NO_SLI, SPAN_FIRST_TOKEN = 1, 2, 4
 SPAN_START = 8
+SPAN_TPOT_SHIFT = 8
+SPAN_TPOT_MAX = (1 << 24) - 1
 assert SPAN.itemsize == 64
+
+
+def span_tpot_us(flags):
+    """The TPOT in microseconds a record's ``flags`` carry (0: none); scalars and arrays alike."""
+    if isinstance(flags, np.ndarray):
+        return flags.astype(np.uint32) >> np.uint32(SPAN_TPOT_SHIFT)
+    return (int(flags) & 0xFFFFFFFF) >> SPAN_TPOT_SHIFT
+
+
+def pack_tpot_us(us):
+    """``us`` (0 .. SPAN_TPOT_MAX, 0: none) as the bits to OR into ``flags``; scalars and arrays alike."""
+    if isinstance(us, np.ndarray):
+        if len(us) and (us.min() < 0 or us.max() > SPAN_TPOT_MAX):
+            raise ValueError("TPOT must be in [0, 2^24 - 1] microseconds")
+        return us.astype(np.uint32) << np.uint32(SPAN_TPOT_SHIFT)
+    if not 0 <= int(us) <= SPAN_TPOT_MAX:
+        raise ValueError("TPOT must be in [0, 2^24 - 1] microseconds")
+    return int(us) << SPAN_TPOT_SHIFT
+
+
+def tpot_us_of_ms(ms) -> int:
+    """A TPOT in float64 ms as the record's integer microseconds: round half up, clamped to
+    1 .. SPAN_TPOT_MAX; 0 (none) for a non-finite or non-positive value."""
+    try:
+        ms = float(ms)
+    except (TypeError, ValueError):
+        return 0
+    if not np.isfinite(ms) or ms <= 0.0:
+        return 0
+    return int(min(SPAN_TPOT_MAX, max(1, int(min(ms, 1e9) * 1000.0 + 0.5))))
 
 FLAG_HAS_GPU = 1 << 8
 FLAG_SYNTHETIC = 1 << 9

@@ -21,6 +21,9 @@ ATTR_SLO_TTFT_EARLY = "llm.slo.ttft_early"
 # open-request tracker counts a TTFT breach when start + SLO passes with no first token
 ATTR_SLO_REQUEST_START ="llm.slo.request_start"
 ATTR_SLO_TOKENS_PER_SEC = "llm.slo.tokens_per_sec"
+# the request's time per output token after the first, ms (the decode-phase SLI; collector/otlp.py
+# derives it from tokens_per_sec or the output token count where a service does not set it)
+ATTR_SLO_TPOT_MS = "llm.slo.tpot_ms"
 ATTR_RETRIEVAL_VECTORDB = "llm.slo.retrieval.vectordb_ms"
 ATTR_RETRIEVAL_NETWORK_MS = "llm.slo.retrieval.network_ms"
 ATTR_RETRIEVAL_DNS_MS = "llm.slo.retrieval.dns_ms"

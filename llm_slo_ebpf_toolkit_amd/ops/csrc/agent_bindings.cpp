@@ -9,6 +9,7 @@
 #include <memory>
 #include <stdexcept>
 
+#include "decodesli.h"
 #include "engine.h"
 #include "exemplars.h"
 #include "onset.h"
@@ -743,6 +744,101 @@ class PyOnsetTracker {
   std::unique_ptr<OnsetTracker> t_;
 };
 
+// The decode-phase SLI tracker (decodesli.h): one step per window over the same span ranges the
+// engine gets; results per step index (pipeline/decodesli.py RESULT_FIELDS).
+class PyDecodeSliTracker {
+ public:
+  PyDecodeSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double slo_ms,
+                     double tpot_slo_ms, bool lds) {
+    if (span_cap < 1) throw std::invalid_argument("decode sli: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("decode sli: the horizon needs more than 2 GiB");
+    decodesli::Config c;
+    c.device = device;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.windows = windows;
+    c.n_buffers = n_buffers;
+    c.slo_ms = slo_ms;
+    c.tpot_slo_ms = tpot_slo_ms;
+    c.lds = lds;
+    decodesli::validate(c);
+    t_ = std::make_unique<DecodeSliTracker>(c);
+  }
+  DecodeSliTracker& t() {
+    if (!t_) throw std::logic_error("decode sli closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    DecodeSliTracker& ds = t();
+    py::gil_scoped_release nogil;
+    return ds.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  // the whole result block of step i as it left the device (uint32 words)
+  py::array_t<uint32_t> block(int64_t i) {
+    DecodeSliTracker& ds = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = ds.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)ds.result_layout().words});
+  }
+  py::dict results(int64_t i, int n_groups) {
+    DecodeSliTracker& ds = t();
+    if (n_groups < 0 || n_groups > ds.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = ds.results(i);
+    }
+    const decodesli::Layout& l = ds.result_layout();
+    const py::ssize_t G = n_groups;
+    py::dict d;
+    d["cells"] = copy_array(r + l.cells, {G, decodesli::kCells});
+    d["cells_roll"] = copy_array(r + l.cells_roll, {G, decodesli::kCells});
+    d["sum_us"] = copy_array(reinterpret_cast<const uint64_t*>(r + l.sum), {G});
+    d["sum_us_roll"] = copy_array(reinterpret_cast<const uint64_t*>(r + l.sum_roll), {G});
+    d["q_win"] = copy_array(r + l.q_win, {G, decodesli::kQuantiles});
+    d["q_roll"] = copy_array(r + l.q_roll, {G, decodesli::kQuantiles});
+    d["stats"] = copy_array(r + l.stats, {decodesli::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (rolling rows u32 [group_cap, K], rolling cells u32 [group_cap, 4], rolling sums u64 [group_cap], ring position)
+  py::tuple resident() {
+    DecodeSliTracker& ds = t();
+    decodesli::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = ds.resident();
+    }
+    const py::ssize_t G = ds.config().group_cap;
+    return py::make_tuple(copy_array(h.rows.data(), {G, decodesli::kK}), copy_array(h.cells.data(), {G, decodesli::kCells}),
+                          copy_array(reinterpret_cast<const uint64_t*>(h.sums.data()), {G}), h.pos);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<DecodeSliTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -858,6 +954,24 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyOnsetTracker::resident)
       .def("sync", &PyOnsetTracker::sync)
       .def("close", &PyOnsetTracker::close);
+  m.attr("DECODESLI_K") = decodesli::kK;
+  m.attr("DECODESLI_STATS") = (int)decodesli::kStats;
+  m.attr("DECODESLI_LDS_SLOTS") = decodesli::kLdsSlots;
+  m.attr("DECODESLI_PER_LANE") = decodesli::kPerLane;
+  m.def("decodesli_bucket_of", [](uint32_t u) { return decodesli::bucket_of(u); });
+  m.def("decodesli_tpot_slo_us", [](double ms) { return decodesli::tpot_slo_us(ms); });
+  py::class_<PyDecodeSliTracker>(m, "DecodeSliTracker")
+      .def(py::init<int, int64_t, int, int, int, double, double, bool>(), py::arg("device") = 0,
+           py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 150, py::arg("n_buffers") = 3,
+           py::arg("slo_ms") = 800.0, py::arg("tpot_slo_ms") = 100.0, py::arg("lds") = true)
+      .def("step", &PyDecodeSliTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyDecodeSliTracker::query)
+      .def("results", &PyDecodeSliTracker::results)
+      .def("block", &PyDecodeSliTracker::block)
+      .def("step_ms", &PyDecodeSliTracker::step_ms)
+      .def("resident", &PyDecodeSliTracker::resident)
+      .def("sync", &PyDecodeSliTracker::sync)
+      .def("close", &PyDecodeSliTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -99,7 +99,7 @@ class WindowPipeline:
                  open_reorder_ms: Optional[float] = None, sli_sketch: int = 0, exemplars: int = 0,
                  exemplar_windows: int = 3, pod_breakdown: int = 0, pod_windows: int = 3, pod_pairs: int = 4096,
                  breach_onset: int = 0, onset_bin_ns: Optional[int] = None, onset_ref_ppm: int = 20000,
-                 onset_alarm: int = 3):
+                 onset_alarm: int = 3, decode_sli: int = 0, tpot_slo_ms: float = 100.0):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -133,7 +133,13 @@ class WindowPipeline:
         with the reference breach rate ``onset_ref_ppm`` (millionths) over it every window and report the
         onset of the current excursion and the bin it reached ``onset_alarm`` excess breaches in
         (pipeline/onset.py; the device tracker for "gpu", the host oracle for "cpu"); ``results()`` then
-        also carries ``onset_rows`` (onset.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
+        also carries ``onset_rows`` (onset.RESULT_KEYS). 0: off, nothing is constructed. One GPU only.
+        ``decode_sli`` > 0: per service, keep the distribution of the time per output token the finished
+        requests' spans carry (records.span_tpot_us) and the 2x2 table of requests by (TTFT above
+        ``ttft_slo_ms``, TPOT above ``tpot_slo_ms``), for every window and for a rolling horizon of that
+        many windows (pipeline/decodesli.py; the device tracker for "gpu", the host oracle for "cpu");
+        ``results()`` then also carries the ``decode_*`` keys (decodesli.RESULT_KEYS). 0: off, nothing is
+        constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -271,6 +277,22 @@ class WindowPipeline:
                 from .onset import OnsetOracle
 
                 self.onset = OnsetOracle(**okw)
+        self.decode = None
+        self._dec: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if decode_sli:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the decode SLI runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            dkw = dict(span_cap=span_cap, group_cap=group_cap, windows=int(decode_sli), n_buffers=self.nb,
+                       slo_ms=ttft_slo_ms, tpot_slo_ms=float(tpot_slo_ms), device=device)
+            if engine == "gpu":
+                from ..ops.decodesli import DecodeSliTracker
+
+                self.decode = DecodeSliTracker(**dkw)
+            else:
+                from .decodesli import DecodeSliOracle
+
+                self.decode = DecodeSliOracle(**dkw)
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -329,7 +351,7 @@ class WindowPipeline:
         tracker is configured -- their steps are queued with the window and read with its results,
         so they keep ``submit``'s order."""
         return bool(getattr(self.eng, "copy_ahead", False)) and all(
-            t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset))
+            t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset, self.decode))
 
     def prepare_copy_ahead(self) -> bool:
         """For the caller that will stage windows in two halves (agent/worker.py): where
@@ -409,6 +431,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(onset_keys(self.onset_results(k, n_groups)))
+        if self.decode is not None:
+            from .decodesli import result_keys as decode_keys
+
+            res = dict(res)
+            res.update(decode_keys(self.decode_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -511,9 +538,29 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- decode SLI (pipeline/decodesli.py) -------------------------------------------------
+    def track_decode(self, spans, n_groups: int) -> None:
+        """The decode SLI tracker's step for the window about to be submitted: the same span ranges.
+        Every window steps (the horizon is counted in windows)."""
+        if self.decode is None:
+            return
+        self._dec[self.k % self.nb] = (self.k, self.decode.step(list(spans), int(n_groups)))
+
+    def decode_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The decode SLI tracker's results of window k (pipeline/decodesli.py RESULT_FIELDS; an empty
+        step's for a window that was submitted past ``track_decode``)."""
+        held = self._dec.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.decode.results(held[1], n_groups)
+        from .decodesli import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.decode is not None:
+            self.decode.close()
         if self.onset is not None:
             self.onset.close()
         if self.pods is not None:
@@ -568,6 +615,8 @@ class WindowPipeline:
             self.pods.sync()
         if self.onset is not None:
             self.onset.sync()
+        if self.decode is not None:
+            self.decode.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -887,6 +936,8 @@ class RingWindowSource:
             pipe.track_pods(spans, n_groups)
         if pipe.onset is not None:  # the breach onset sees the window's spans and the cut's time
             pipe.track_onset(spans, cut.t_ns, n_groups)
+        if pipe.decode is not None:  # the decode SLI sees the window's spans
+            pipe.track_decode(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
