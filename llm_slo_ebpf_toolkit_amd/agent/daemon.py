@@ -241,6 +241,16 @@ class AgentOptions:
     decode_sli: bool = False
     tpot_slo_ms: float = 100.0           # the TPOT SLO (reasoned, not measured, untuned: 10 tokens/s)
     decode_horizon_windows: int = 0      # windows of the rolling horizon (0: the TTFT sketch's)
+    # per service, a rolling two-sample test of the TTFT distribution of the last windows against a trailing
+    # baseline of calm windows, decided on the GPU every window (pipeline/drift.py, docs/TTFT_DRIFT.md): a drift
+    # field in the decision log and four series; one GPU; nothing is checkpointed (warming after a restart)
+    ttft_drift: bool = False
+    emit_on_drift: bool = False          # needs ttft_drift: the emission gate becomes "burning or slow"
+    drift_recent_windows: int = 0        # R (0: 10 s of windows)
+    drift_gap_windows: int = 0           # L (0: 10 s of windows)
+    drift_baseline_windows: int = 0      # B (0: 300 s of windows)
+    drift_crit: float = 4.0              # c^2, the test's critical value (reasoned, untuned)
+    drift_min_shift_buckets: int = 2     # s: p50 or p90 must have moved this many buckets, 1/16 octave each (untuned)
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -732,6 +742,8 @@ class Agent:
         rec_n = int(self.o.emit_recovered_requests)
         if rec_n < 0:  # 4 requests per 1 s window (the first recovery windows of config 3), at least 2
             rec_n = max(2, int(round(4 * self.o.window_ms / 1000.0)))
+        drift_state = res.get("drift_state") if res.get("drift_state") is not None else ()
+        drift_on = bool(self.o.emit_on_drift) and res.get("drift_state") is not None
         for g in range(G):
             if g < len(reqs) and reqs[g] == 0 and not (g < len(late_l) and late_l[g]):
                 continue  # no request of this group in the window: no incident to attribute
@@ -746,7 +758,10 @@ class Agent:
                          and sli[g, 0] >= rec_n and sli[g, 1] == 0)
             burning = (sli is None or self.o.emit_min_burn <= 0
                        or (cur > 0 and cur >= self.o.emit_min_burn * (1.0 - 1e-9)))
-            emit = confident and burning and not recovered
+            # --emit-on-drift: a service whose TTFT distribution is significantly slower than its baseline
+            # passes the gate without burning; confident and recovered stay what they are
+            drifting = drift_on and g < len(drift_state) and bool(int(drift_state[g]) & 1)
+            emit = confident and (burning or drifting) and not recovered
             ranked = model.ranked(post[g, :D], bits[g, :D]) if (emit or log is not None) else None
             if log is not None:
                 log.write(json.dumps({
@@ -768,8 +783,11 @@ class Agent:
                        and g < len(res["onset_rows"]) else {}),
                     **({"decode": self._decode_entry(res, g)} if res.get("decode_cells") is not None
                        and g < len(res["decode_cells"]) else {}),
+                    **({"drift": self._drift_entry(res, g)} if res.get("drift_state") is not None
+                       and g < len(res["drift_state"]) else {}),
+                    **({"gate": "burn" if burning else "drift"} if emit and drift_on else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
-                                                   ("no_burn" if not burning else "recovered"))}) + "\n")
+                                                   ("no_burn" if not (burning or drifting) else "recovered"))}) + "\n")
             if not confident:
                 continue
             self.metrics.observe_incident(catalog.ALL_DOMAINS[top_d[g]], emit)
@@ -867,6 +885,24 @@ class Agent:
         return {**summary(res["decode_cells"][g], res["decode_sum_ms"][g], res["decode_q"][g]),
                 "horizon": summary(res["decode_cells_roll"][g], res["decode_sum_ms_roll"][g], res["decode_q_roll"][g])}
 
+    def drift_windows(self) -> Tuple[int, int, int]:
+        """(R, L, B) of the TTFT drift tracker: the flags, or 10 s / 10 s / 300 s of windows."""
+        from ..pipeline.drift import defaults
+
+        d = defaults(float(self.o.window_ms))
+        given = (int(self.o.drift_recent_windows), int(self.o.drift_gap_windows), int(self.o.drift_baseline_windows))
+        return tuple(g if g > 0 else x for g, x in zip(given, d))
+
+    @staticmethod
+    def _drift_entry(res: dict, g: int) -> dict:
+        """Group g's TTFT drift for the decision log: the state, the one-sided distance, the sizes of the two
+        samples, p50 / p90 as [base, recent] in ms (``None`` where a sample is empty) and the windows held."""
+        from ..pipeline.drift import summary
+
+        s = summary(res["drift_state"][g], res["drift_hold"][g], res["drift_n_recent"][g], res["drift_n_base"][g],
+                    res["drift_slow_num"][g], res["drift_q_recent"][g], res["drift_q_base"][g])
+        return {k: s[k] for k in ("state", "distance", "n_recent", "n_base", "p50_ms", "p90_ms", "held_windows")}
+
     def _exemplar_ids(self, res: dict, g: int) -> dict:
         """``request_ids`` (span ids) and ``trace_ids`` (de-duplicated, order kept) of group g's recent
         exemplars beyond the TTFT SLO; nothing when none is, or the tracker is off."""
@@ -943,7 +979,9 @@ class Agent:
             self.metrics.observe_onset(res, head["breach_onset"], names, t_ns, self.onset_bin_ns())
         if head.get("decode_sli") is not None and res.get("decode_cells") is not None:
             self.metrics.observe_decode(res, head["decode_sli"], names)
-        attrs =self._attributions(G, names, res, t_ns, model)
+        if head.get("ttft_drift") is not None and res.get("drift_state") is not None:
+            self.metrics.observe_drift(res, head["ttft_drift"], names)
+        attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
             self.writers.emit_attribution(attr)
@@ -1066,6 +1104,11 @@ class Agent:
         if o.decode_sli and N > 1:
             raise ValueError("--decode-sli runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the decode SLI tracker's are read on the host")
+        if o.emit_on_drift and not o.ttft_drift:
+            raise ValueError("--emit-on-drift needs --ttft-drift")
+        if o.ttft_drift and N > 1:
+            raise ValueError("--ttft-drift runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the TTFT drift tracker's are read on the host")
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1118,7 +1161,9 @@ class Agent:
                             breach_onset=int(o.onset_bins) if o.breach_onset else 0,
                             onset_bin_ns=self.onset_bin_ns(), onset_ref_ppm=self.onset_ref_ppm(),
                             onset_alarm=int(o.onset_alarm_breaches),
-                            decode_sli=self.decode_horizon() if o.decode_sli else 0, tpot_slo_ms=float(o.tpot_slo_ms))
+                            decode_sli=self.decode_horizon() if o.decode_sli else 0, tpot_slo_ms=float(o.tpot_slo_ms),
+                            ttft_drift=self.drift_windows() if o.ttft_drift else None, drift_crit=float(o.drift_crit),
+                            drift_min_shift=int(o.drift_min_shift_buckets))
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

@@ -167,6 +167,21 @@ class AgentMetrics:
                                        "Decode SLI events: invalid (a TPOT with a NaN or negative TTFT), out_of_group (a "
                                        "group beyond the window's), no_decode (a finished request without a TPOT).",
                                        ("reason",))
+        # TTFT drift (agent --ttft-drift, pipeline/drift.py): recent against baseline
+        self.drift_state = r.gauge("llm_slo_agent_ttft_drift_state",
+                                   "TTFT drift of the service: 0 calm, 1 slow (the recent windows are significantly and "
+                                   "materially slower than the baseline), 2 fast, 3 warming (too few records or baseline "
+                                   "windows; also the window of a rebase).", ("service",))
+        self.drift_distance = r.gauge("llm_slo_agent_ttft_drift_distance",
+                                      "One-sided two-sample Kolmogorov-Smirnov distance of the service's recent TTFT "
+                                      "distribution towards slower than its baseline, 0..1.", ("service",))
+        self.drift_ratio = r.gauge("llm_slo_agent_ttft_drift_shift_ratio",
+                                   "Recent p50 TTFT over the baseline's p50, by service.", ("service",))
+        self.drift_events = r.counter("llm_slo_agent_ttft_drift_events_total",
+                                      "TTFT drift events: invalid (ttft NaN or negative), out_of_group (a group beyond the "
+                                      "window's), admitted / withheld (a window leaving the gap entered the baseline / was "
+                                      "kept out while the service was slow), rebased (a baseline dropped after hold_max "
+                                      "slow windows).", ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -364,6 +379,23 @@ class AgentMetrics:
                     self.tpot_quantile.set(v, name, q)
         for reason in EVENT_STATS:
             self.decode_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_drift(self, res: dict, stats: dict, names) -> None:
+        """One window of the TTFT drift tracker: ``res`` carries the drift_* arrays per group
+        (pipeline/drift.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.drift import EVENT_STATS, FAST, SLOW, WARMING, summary
+
+        for g, st in enumerate(np.asarray(res["drift_state"], dtype=np.int64).tolist()):
+            name = names[g] if g < len(names) else f"group-{g}"
+            self.drift_state.set(3.0 if st & WARMING else 1.0 if st & SLOW else 2.0 if st & FAST else 0.0, name)
+            s = summary(st, res["drift_hold"][g], res["drift_n_recent"][g], res["drift_n_base"][g], res["drift_slow_num"][g],
+                        res["drift_q_recent"][g], res["drift_q_base"][g])
+            if s["distance"] is not None:  # an empty sample keeps the last values: NaN would break max()
+                self.drift_distance.set(float(s["distance"]), name)
+            if s["shift_ratio"] is not None:
+                self.drift_ratio.set(float(s["shift_ratio"]), name)
+        for reason in EVENT_STATS:
+            self.drift_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

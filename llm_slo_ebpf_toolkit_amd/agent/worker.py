@@ -93,12 +93,18 @@ class WorkerSpec:
     onset_alarm: int = 3        # excess breaches that count as an alarm (agent --onset-alarm-breaches)
     decode_sli: int = 0         # windows of the decode SLI's rolling horizon (agent --decode-sli); 0: off
     tpot_slo_ms: float = 100.0  # the TPOT SLO (agent --tpot-slo-ms)
+    ttft_drift: Optional[Tuple[int, int, int]] = None  # (R, L, B) of the TTFT drift tracker (agent --ttft-drift); None: off
+    drift_crit: float = 4.0     # c^2 (agent --drift-crit)
+    drift_min_shift: int = 2    # s, buckets (agent --drift-min-shift-buckets)
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
 POD_RESULT_KEYS = tuple(f"pod_{s}_{f}" for s in ("win", "rec") for f in ("n", "b", "pods", "pods_b", "k_top", "top"))
 # the decode SLI's (pipeline/decodesli.py RESULT_KEYS)
 DECODE_RESULT_KEYS = ("decode_cells", "decode_cells_roll", "decode_sum_ms", "decode_sum_ms_roll", "decode_q", "decode_q_roll")
+# the TTFT drift's (pipeline/drift.py RESULT_KEYS)
+DRIFT_RESULT_KEYS = ("drift_state", "drift_hold", "drift_n_win", "drift_n_recent", "drift_n_base", "drift_base_fill",
+                     "drift_slow_num", "drift_fast_num", "drift_q_recent", "drift_q_base")
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -113,7 +119,8 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     out = {}
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
-                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS):
+                "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS,
+                *DRIFT_RESULT_KEYS):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -188,7 +195,8 @@ class WorkerCore:
                                    pod_pairs=spec.pod_pairs, breach_onset=spec.breach_onset,
                                    onset_bin_ns=spec.onset_bin_ns, onset_ref_ppm=spec.onset_ref_ppm,
                                    onset_alarm=spec.onset_alarm, decode_sli=spec.decode_sli,
-                                   tpot_slo_ms=spec.tpot_slo_ms)
+                                   tpot_slo_ms=spec.tpot_slo_ms, ttft_drift=spec.ttft_drift,
+                                   drift_crit=spec.drift_crit, drift_min_shift=spec.drift_min_shift)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -366,6 +374,10 @@ class WorkerCore:
                 from ..pipeline.decodesli import stats_dict as decode_stats
 
                 d["decode_sli"] = decode_stats(pipe.decode_results(k, n_groups)["stats"])
+            if pipe.drift is not None:  # the TTFT drift tracker's statistics of the window
+                from ..pipeline.drift import stats_dict as drift_stats
+
+                d["ttft_drift"] = drift_stats(pipe.drift_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

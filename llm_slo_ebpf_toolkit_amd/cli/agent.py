@@ -156,6 +156,22 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                        "untuned: 10 tokens/s is about the slowest stream a reader does not outpace)"),
         ("decode-horizon-windows", d.decode_horizon_windows, "--decode-sli: windows of the rolling horizon (0 = "
                                                              "--ttft-horizon-windows' value)"),
+        ("ttft-drift", False, "gpu engine: per service, compare the TTFT distribution of the last "
+                              "--drift-recent-windows windows with a trailing baseline of calm windows by an integer "
+                              "two-sample test on the GPU every window: a fault that moves TTFT towards the SLO without "
+                              "crossing it shows as slow -- a drift field in the decision log, "
+                              "llm_slo_agent_ttft_drift_state / _distance / _shift_ratio{service}; one GPU only; the "
+                              "rings are not checkpointed (warming after a restart)"),
+        ("emit-on-drift", False, "--ttft-drift: the emission gate becomes 'burning or slow' (the decision log's gate "
+                                 "says which); confidence and the recovered rule stay as they are"),
+        ("drift-recent-windows", d.drift_recent_windows, "--ttft-drift: R, windows of the recent sample (0 = 10 s)"),
+        ("drift-gap-windows", d.drift_gap_windows, "--ttft-drift: L, windows between the recent sample and the "
+                                                   "baseline (0 = 10 s)"),
+        ("drift-baseline-windows", d.drift_baseline_windows, "--ttft-drift: B, calm non-empty windows of the baseline "
+                                                             "(0 = 300 s)"),
+        ("drift-crit", d.drift_crit, "--ttft-drift: c^2, the critical value of D^2 n_e (reasoned, untuned)"),
+        ("drift-min-shift-buckets", d.drift_min_shift_buckets, "--ttft-drift: buckets (1/16 octave each) p50 or p90 "
+                                                               "must have moved (untuned: 2 is about 6 percent)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -213,6 +229,10 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         onset_ref_burn=float(a.onset_ref_burn), onset_alarm_breaches=int(a.onset_alarm_breaches),
         decode_sli=bool(a.decode_sli), tpot_slo_ms=float(a.tpot_slo_ms),
         decode_horizon_windows=int(a.decode_horizon_windows),
+        ttft_drift=bool(a.ttft_drift), emit_on_drift=bool(a.emit_on_drift),
+        drift_recent_windows=int(a.drift_recent_windows), drift_gap_windows=int(a.drift_gap_windows),
+        drift_baseline_windows=int(a.drift_baseline_windows), drift_crit=float(a.drift_crit),
+        drift_min_shift_buckets=int(a.drift_min_shift_buckets),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "decodesli.h"
+#include "drift.h"
 #include "engine.h"
 #include "exemplars.h"
 #include "onset.h"
@@ -839,6 +840,115 @@ class PyDecodeSliTracker {
   std::unique_ptr<DecodeSliTracker> t_;
 };
 
+// The TTFT drift tracker (drift.h): one step per window over the same span ranges the engine gets;
+// results per step index (pipeline/drift.py RESULT_FIELDS).
+class PyDriftTracker {
+ public:
+  PyDriftTracker(int device, int64_t span_cap, int group_cap, int recent, int gap, int baseline, int n_buffers, double crit,
+                 int min_shift, int64_t min_recent, int64_t min_base, int min_base_windows, int64_t hold_max, bool lds) {
+    if (span_cap < 1) throw std::invalid_argument("ttft drift: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31))
+      throw std::invalid_argument("ttft drift: span_cap^2 * recent * baseline must stay below 2^44 (slow_num << 16 would wrap)");
+    drift::Config c;
+    c.device = device;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.recent = recent;
+    c.gap = gap;
+    c.baseline = baseline;
+    c.n_buffers = n_buffers;
+    c.crit = crit;
+    c.min_shift = min_shift;
+    c.min_recent = min_recent;
+    c.min_base = min_base;
+    c.min_base_windows = min_base_windows;
+    c.hold_max = hold_max;
+    c.lds = lds;
+    drift::validate(c);
+    t_ = std::make_unique<DriftTracker>(c);
+  }
+  DriftTracker& t() {
+    if (!t_) throw std::logic_error("ttft drift closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    DriftTracker& dt = t();
+    py::gil_scoped_release nogil;
+    return dt.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  // the whole result block of step i as it left the device (uint32 words)
+  py::array_t<uint32_t> block(int64_t i) {
+    DriftTracker& dt = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = dt.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)dt.result_layout().words});
+  }
+  py::dict results(int64_t i, int n_groups) {
+    DriftTracker& dt = t();
+    if (n_groups < 0 || n_groups > dt.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = dt.results(i);
+    }
+    const drift::Layout& l = dt.result_layout();
+    const py::ssize_t G = n_groups;
+    py::dict d;
+    d["n_win"] = copy_array(r + l.n_win, {G});
+    d["n_recent"] = copy_array(r + l.n_recent, {G});
+    d["n_base"] = copy_array(r + l.n_base, {G});
+    d["base_fill"] = copy_array(r + l.base_fill, {G});
+    d["q_recent"] = copy_array(r + l.q_recent, {G, drift::kQuantiles});
+    d["q_base"] = copy_array(r + l.q_base, {G, drift::kQuantiles});
+    d["slow_num"] = copy_array(reinterpret_cast<const uint64_t*>(r + l.slow_num), {G});
+    d["fast_num"] = copy_array(reinterpret_cast<const uint64_t*>(r + l.fast_num), {G});
+    d["slow_at"] = copy_array(r + l.slow_at, {G});
+    d["fast_at"] = copy_array(r + l.fast_at, {G});
+    d["state"] = copy_array(r + l.state, {G});
+    d["hold"] = copy_array(r + l.hold, {G});
+    d["stats"] = copy_array(r + l.stats, {drift::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (recent u32 [group_cap, row stride], base alike, base_fill, base_pos, hold u32 [group_cap], near-ring position)
+  py::tuple resident() {
+    DriftTracker& dt = t();
+    drift::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = dt.resident();
+    }
+    const py::ssize_t G = dt.config().group_cap;
+    return py::make_tuple(copy_array(h.recent.data(), {G, drift::kRowStride}), copy_array(h.base.data(), {G, drift::kRowStride}),
+                          copy_array(h.base_fill.data(), {G}), copy_array(h.base_pos.data(), {G}),
+                          copy_array(h.hold.data(), {G}), h.pos);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<DriftTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -972,6 +1082,51 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyDecodeSliTracker::resident)
       .def("sync", &PyDecodeSliTracker::sync)
       .def("close", &PyDecodeSliTracker::close);
+  m.attr("DRIFT_K") = drift::kK;
+  m.attr("DRIFT_ROW_STRIDE") = drift::kRowStride;
+  m.attr("DRIFT_STATS") = (int)drift::kStats;
+  m.attr("DRIFT_LDS_SLOTS") = drift::kLdsSlots;
+  m.attr("DRIFT_PER_LANE") = drift::kPerLane;
+  m.attr("DRIFT_SLOW") = drift::kSlow;
+  m.attr("DRIFT_FAST") = drift::kFast;
+  m.attr("DRIFT_WARMING") = drift::kWarming;
+  m.attr("DRIFT_REBASED") = drift::kRebased;
+  m.def("drift_crit_q", [](double c2) { return drift::crit_q(c2); });
+  // the state bits of one service before hold and reset (drift_host.h decide), for a host-side cross-check
+  m.def(
+      "drift_decide",
+      [](uint32_t n_r, uint32_t n_b, uint32_t base_fill, uint64_t slow_num, uint64_t fast_num,
+         const std::vector<uint32_t>& q_recent, const std::vector<uint32_t>& q_base, double crit, uint32_t min_shift,
+         uint32_t min_recent, uint32_t min_base, uint32_t min_base_windows) {
+        if (q_recent.size() != (size_t)drift::kQuantiles || q_base.size() != (size_t)drift::kQuantiles)
+          throw std::invalid_argument("drift_decide: four quantile buckets a row");
+        if ((uint64_t)n_r * n_b >= (uint64_t(1) << 44) || slow_num > (uint64_t)n_r * n_b || fast_num > (uint64_t)n_r * n_b)
+          throw std::invalid_argument("drift_decide: n_r * n_b must stay below 2^44 and bound the numerators");
+        drift::Thresholds t;
+        t.crit_q = drift::crit_q(crit);
+        t.min_shift = min_shift;
+        t.min_recent = min_recent;
+        t.min_base = min_base;
+        t.min_base_windows = min_base_windows;
+        return drift::decide(n_r, n_b, base_fill, slow_num, fast_num, q_recent.data(), q_base.data(), t);
+      },
+      py::arg("n_r"), py::arg("n_b"), py::arg("base_fill"), py::arg("slow_num"), py::arg("fast_num"), py::arg("q_recent"),
+      py::arg("q_base"), py::arg("crit") = 4.0, py::arg("min_shift") = 2, py::arg("min_recent") = 30,
+      py::arg("min_base") = 100, py::arg("min_base_windows") = 10);
+  py::class_<PyDriftTracker>(m, "DriftTracker")
+      .def(py::init<int, int64_t, int, int, int, int, int, double, int, int64_t, int64_t, int, int64_t, bool>(),
+           py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("recent") = 10,
+           py::arg("gap") = 10, py::arg("baseline") = 300, py::arg("n_buffers") = 3, py::arg("crit") = 4.0,
+           py::arg("min_shift") = 2, py::arg("min_recent") = 30, py::arg("min_base") = 100,
+           py::arg("min_base_windows") = 10, py::arg("hold_max") = 1200, py::arg("lds") = true)
+      .def("step", &PyDriftTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyDriftTracker::query)
+      .def("results", &PyDriftTracker::results)
+      .def("block", &PyDriftTracker::block)
+      .def("step_ms", &PyDriftTracker::step_ms)
+      .def("resident", &PyDriftTracker::resident)
+      .def("sync", &PyDriftTracker::sync)
+      .def("close", &PyDriftTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

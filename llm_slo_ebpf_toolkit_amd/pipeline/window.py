@@ -99,7 +99,11 @@ class WindowPipeline:
                  open_reorder_ms: Optional[float] = None, sli_sketch: int = 0, exemplars: int = 0,
                  exemplar_windows: int = 3, pod_breakdown: int = 0, pod_windows: int = 3, pod_pairs: int = 4096,
                  breach_onset: int = 0, onset_bin_ns: Optional[int] = None, onset_ref_ppm: int = 20000,
-                 onset_alarm: int = 3, decode_sli: int = 0, tpot_slo_ms: float = 100.0):
+                 onset_alarm: int = 3, decode_sli: int = 0, tpot_slo_ms: float = 100.0,
+                 ttft_drift: Optional[Tuple[int, int, int]] = None, drift_crit: Optional[float] = None,
+                 drift_min_shift: Optional[int] = None, drift_min_recent: Optional[int] = None,
+                 drift_min_base: Optional[int] = None, drift_min_base_windows: Optional[int] = None,
+                 drift_hold_max: Optional[int] = None):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -139,7 +143,15 @@ class WindowPipeline:
         ``ttft_slo_ms``, TPOT above ``tpot_slo_ms``), for every window and for a rolling horizon of that
         many windows (pipeline/decodesli.py; the device tracker for "gpu", the host oracle for "cpu");
         ``results()`` then also carries the ``decode_*`` keys (decodesli.RESULT_KEYS). 0: off, nothing is
-        constructed. One GPU only."""
+        constructed. One GPU only.
+        ``ttft_drift`` = (R, L, B): per service, compare the TTFT distribution of the last R windows with
+        that of the last B calm, non-empty windows at least L windows further back, by an integer one-sided
+        two-sample Kolmogorov-Smirnov test with the critical value ``drift_crit`` (c^2) and a minimum
+        quantile shift of ``drift_min_shift`` buckets; ``drift_min_recent`` / ``drift_min_base`` /
+        ``drift_min_base_windows`` are what a decision needs, ``drift_hold_max`` the consecutive slow windows
+        after which the baseline is dropped (``None``: pipeline/drift.py's defaults; the device tracker for
+        "gpu", the host oracle for "cpu"); ``results()`` then also carries the ``drift_*`` keys
+        (drift.RESULT_KEYS). ``None``: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -293,6 +305,27 @@ class WindowPipeline:
                 from .decodesli import DecodeSliOracle
 
                 self.decode = DecodeSliOracle(**dkw)
+        self.drift = None
+        self._drf: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if ttft_drift:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the TTFT drift runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            R_, L_, B_ = (int(x) for x in ttft_drift)
+            fkw = dict(span_cap=span_cap, group_cap=group_cap, recent=R_, gap=L_, baseline=B_, n_buffers=self.nb,
+                       crit=drift_crit, min_shift=drift_min_shift, min_recent=drift_min_recent, min_base=drift_min_base,
+                       min_base_windows=drift_min_base_windows, hold_max=drift_hold_max, device=device)
+            if engine == "gpu":
+                from ..ops.drift import DriftTracker
+
+                self.drift = DriftTracker(**fkw)
+            else:
+                from .drift import DriftOracle
+
+                self.drift = DriftOracle(**fkw)
+        # the side trackers are fixed from here on: copy_ahead asks once per window and half
+        self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
+                                                        self.decode, self.drift))
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -350,8 +383,7 @@ class WindowPipeline:
         engine offers it (ops/csrc/engine.h ``copy_ahead``: overlapped windows on one GPU) and no side
         tracker is configured -- their steps are queued with the window and read with its results,
         so they keep ``submit``'s order."""
-        return bool(getattr(self.eng, "copy_ahead", False)) and all(
-            t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset, self.decode))
+        return self._no_side_tracker and bool(getattr(self.eng, "copy_ahead", False))
 
     def prepare_copy_ahead(self) -> bool:
         """For the caller that will stage windows in two halves (agent/worker.py): where
@@ -436,6 +468,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(decode_keys(self.decode_results(k, n_groups)))
+        if self.drift is not None:
+            from .drift import result_keys as drift_keys
+
+            res = dict(res)
+            res.update(drift_keys(self.drift_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -556,9 +593,29 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- TTFT drift (pipeline/drift.py) -----------------------------------------------------
+    def track_drift(self, spans, n_groups: int) -> None:
+        """The drift tracker's step for the window about to be submitted: the same span ranges. Every
+        window steps (the rings are counted in windows)."""
+        if self.drift is None:
+            return
+        self._drf[self.k % self.nb] = (self.k, self.drift.step(list(spans), int(n_groups)))
+
+    def drift_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The drift tracker's results of window k (pipeline/drift.py RESULT_FIELDS; an empty step's for a
+        window that was submitted past ``track_drift``)."""
+        held = self._drf.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.drift.results(held[1], n_groups)
+        from .drift import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.drift is not None:
+            self.drift.close()
         if self.decode is not None:
             self.decode.close()
         if self.onset is not None:
@@ -617,6 +674,8 @@ class WindowPipeline:
             self.onset.sync()
         if self.decode is not None:
             self.decode.sync()
+        if self.drift is not None:
+            self.drift.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -938,6 +997,8 @@ class RingWindowSource:
             pipe.track_onset(spans, cut.t_ns, n_groups)
         if pipe.decode is not None:  # the decode SLI sees the window's spans
             pipe.track_decode(spans, n_groups)
+        if pipe.drift is not None:  # the TTFT drift sees the window's spans
+            pipe.track_drift(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
