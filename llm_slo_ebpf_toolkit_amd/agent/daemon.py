@@ -251,6 +251,17 @@ class AgentOptions:
     drift_baseline_windows: int = 0      # B (0: 300 s of windows)
     drift_crit: float = 4.0              # c^2, the test's critical value (reasoned, untuned)
     drift_min_shift_buckets: int = 2     # s: p50 or p90 must have moved this many buckets, 1/16 octave each (untuned)
+    # per service, the finished requests by the outcome class their spans carry and a multi-window,
+    # multi-burn-rate evaluation of the availability error budget, decided on the GPU every window
+    # (pipeline/errsli.py, docs/ERROR_SLI.md): an errors field in the decision log and five series; one GPU;
+    # nothing is checkpointed (a restart forgets the horizon). The defaults are reasoned, not tuned
+    error_sli: bool = False
+    error_slo_target: float = 0.999      # the availability target
+    error_burn_pairs: str = "3600:300:14.4,21600:1800:6"  # long_s:short_s:factor (the SRE workbook's paging pairs)
+    error_min_requests: int = 20         # fewest requests in a pair's window for it to burn
+    error_bad_classes: str = "throttled,timeout,unavailable,server,other"  # client and cancelled are the caller's
+    error_horizon_windows: int = 0       # windows of the rolling horizon (0: the longest pair)
+    emit_on_error_burn: bool = False     # needs error_sli: the emission gate becomes "burning or a pair fires"
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -744,9 +755,19 @@ class Agent:
             rec_n = max(2, int(round(4 * self.o.window_ms / 1000.0)))
         drift_state = res.get("drift_state") if res.get("drift_state") is not None else ()
         drift_on = bool(self.o.emit_on_drift) and res.get("drift_state") is not None
+        err_on = bool(self.o.emit_on_error_burn) and res.get("err_firing") is not None
+        err_firing = res.get("err_firing") if res.get("err_firing") is not None else ()
+        err_n = err_bad = ()
+        if res.get("err_counts") is not None:
+            bad_cols = [j for j in range(8) if (self.error_bad_mask() >> j) & 1]
+            ec = np.asarray(res["err_counts"], dtype=np.int64)
+            err_n, err_bad = ec.sum(axis=1).tolist(), ec[:, bad_cols].sum(axis=1).tolist()
         for g in range(G):
-            if g < len(reqs) and reqs[g] == 0 and not (g < len(late_l) and late_l[g]):
-                continue  # no request of this group in the window: no incident to attribute
+            if (g < len(reqs) and reqs[g] == 0 and not (g < len(late_l) and late_l[g])
+                    and not (g < len(err_n) and err_n[g])):
+                # no request of this group in the window: no incident to attribute (with --error-sli a request
+                # that finished without a TTFT, as a fast failure does, is one)
+                continue
             burn = forecast.get(g, 0.0)  # forecast burn over the SLO window (measured counts)
             # (1 - 1e-9: the budget 1 - target is not exact in binary, a burn of exactly 1 lands a hair under)
             cur = now_burn.get(g, 0.0)
@@ -761,7 +782,13 @@ class Agent:
             # --emit-on-drift: a service whose TTFT distribution is significantly slower than its baseline
             # passes the gate without burning; confident and recovered stay what they are
             drifting = drift_on and g < len(drift_state) and bool(int(drift_state[g]) & 1)
-            emit = confident and (burning or drifting) and not recovered
+            # --emit-on-error-burn: a service with a firing burn-rate pair of the availability budget passes
+            # too. recovered would hold back exactly the fast failures (requests done, no TTFT breach): where
+            # the error gate is what opened the window and the window itself holds a failure, it does not apply
+            erring = err_on and g < len(err_firing) and int(err_firing[g]) != 0
+            if erring and not burning and g < len(err_bad) and err_bad[g] > 0:
+                recovered = False
+            emit = confident and (burning or erring or drifting) and not recovered
             ranked = model.ranked(post[g, :D], bits[g, :D]) if (emit or log is not None) else None
             if log is not None:
                 log.write(json.dumps({
@@ -785,9 +812,13 @@ class Agent:
                        and g < len(res["decode_cells"]) else {}),
                     **({"drift": self._drift_entry(res, g)} if res.get("drift_state") is not None
                        and g < len(res["drift_state"]) else {}),
-                    **({"gate": "burn" if burning else "drift"} if emit and drift_on else {}),
+                    **({"errors": self._error_entry(res, g)} if res.get("err_counts") is not None
+                       and g < len(res["err_counts"]) else {}),
+                    **({"gate": "burn" if burning else ("errors" if erring else "drift")}
+                       if emit and (drift_on or err_on) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
-                                                   ("no_burn" if not (burning or drifting) else "recovered"))}) + "\n")
+                                                   ("no_burn" if not (burning or erring or drifting)
+                                                    else "recovered"))}) + "\n")
             if not confident:
                 continue
             self.metrics.observe_incident(catalog.ALL_DOMAINS[top_d[g]], emit)
@@ -885,6 +916,35 @@ class Agent:
         return {**summary(res["decode_cells"][g], res["decode_sum_ms"][g], res["decode_q"][g]),
                 "horizon": summary(res["decode_cells_roll"][g], res["decode_sum_ms_roll"][g], res["decode_q_roll"][g])}
 
+    def error_pairs(self) -> list:
+        """The burn-rate pairs as (long windows, short windows, factor_milli) of this agent's windows."""
+        from ..pipeline.errsli import parse_pairs
+
+        p = getattr(self, "_error_pairs", None)
+        if p is None:  # asked per scored group and window
+            p = self._error_pairs = parse_pairs(self.o.error_burn_pairs, float(self.o.window_ms))
+        return list(p)
+
+    def error_horizon(self) -> int:
+        """Windows of the error SLI's rolling horizon: the flag, or the longest pair."""
+        w = int(self.o.error_horizon_windows)
+        return w if w > 0 else max(p[0] for p in self.error_pairs())
+
+    def error_bad_mask(self) -> int:
+        from ..pipeline.errsli import bad_mask_of
+
+        m = getattr(self, "_error_bad_mask", None)
+        if m is None:
+            m = self._error_bad_mask = bad_mask_of(self.o.error_bad_classes)
+        return m
+
+    def _error_entry(self, res: dict, g: int) -> dict:
+        """Group g's error SLI for the decision log: the window's and the horizon's requests by class, the
+        burn rates of every pair's two windows and which pairs fire; ``None`` where there is no request."""
+        from ..pipeline.errsli import budget_ppm, summary
+
+        return summary(res, g, self.error_pairs(), budget_ppm(float(self.o.error_slo_target)), self.error_bad_mask())
+
     def drift_windows(self) -> Tuple[int, int, int]:
         """(R, L, B) of the TTFT drift tracker: the flags, or 10 s / 10 s / 300 s of windows."""
         from ..pipeline.drift import defaults
@@ -981,6 +1041,11 @@ class Agent:
             self.metrics.observe_decode(res, head["decode_sli"], names)
         if head.get("ttft_drift") is not None and res.get("drift_state") is not None:
             self.metrics.observe_drift(res, head["ttft_drift"], names)
+        if head.get("error_sli") is not None and res.get("err_counts") is not None:
+            from ..pipeline.errsli import budget_ppm
+
+            self.metrics.observe_errors(res, head["error_sli"], names, self.error_pairs(),
+                                        budget_ppm(float(self.o.error_slo_target)), self.error_bad_mask())
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -1109,6 +1174,13 @@ class Agent:
         if o.ttft_drift and N > 1:
             raise ValueError("--ttft-drift runs on one GPU (--gpus 1): the workers' results are gathered on "
                              "the device, the TTFT drift tracker's are read on the host")
+        if o.emit_on_error_burn and not o.error_sli:
+            raise ValueError("--emit-on-error-burn needs --error-sli")
+        if o.error_sli and N > 1:
+            raise ValueError("--error-sli runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the error SLI tracker's are read on the host")
+        if o.error_sli:  # a pair beyond the horizon's cap, an unknown class: refused here, by name
+            self.error_pairs(), self.error_bad_mask()
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1163,7 +1235,12 @@ class Agent:
                             onset_alarm=int(o.onset_alarm_breaches),
                             decode_sli=self.decode_horizon() if o.decode_sli else 0, tpot_slo_ms=float(o.tpot_slo_ms),
                             ttft_drift=self.drift_windows() if o.ttft_drift else None, drift_crit=float(o.drift_crit),
-                            drift_min_shift=int(o.drift_min_shift_buckets))
+                            drift_min_shift=int(o.drift_min_shift_buckets),
+                            error_sli=self.error_horizon() if o.error_sli else 0,
+                            error_target=float(o.error_slo_target),
+                            error_pairs=tuple(self.error_pairs()) if o.error_sli else None,
+                            error_min_requests=int(o.error_min_requests),
+                            error_bad_mask=self.error_bad_mask() if o.error_sli else 0xF8)
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):
@@ -1200,7 +1277,7 @@ class Agent:
                         ipcache["t"] = time.monotonic()
                     return ipcache["m"]
             mapper = SpanMapper(groups, self.pod_ids.id, node_id, pod_ips=pod_ips, forwarders=o.otlp_forwarders,
-                                decode_sli=bool(o.decode_sli))
+                                decode_sli=bool(o.decode_sli), error_sli=bool(o.error_sli))
             mapper.slo_ms = float(o.ttft_slo_ms)
             mapper.keep_trace_high = bool(o.request_exemplars)  # exemplars quote the whole W3C trace id
             self.mapper = mapper

@@ -182,6 +182,22 @@ class AgentMetrics:
                                       "window's), admitted / withheld (a window leaving the gap entered the baseline / was "
                                       "kept out while the service was slow), rebased (a baseline dropped after hold_max "
                                       "slow windows).", ("reason",))
+        # error SLI (agent --error-sli, pipeline/errsli.py): outcome classes and budget burn
+        self.outcomes = r.counter("llm_slo_agent_request_outcomes_total",
+                                  "Finished requests by service and outcome class: ok, client, cancelled, throttled, "
+                                  "timeout, unavailable, server, other.", ("service", "outcome"))
+        self.error_ratio = r.gauge("llm_slo_agent_error_ratio",
+                                   "Share of the service's finished requests over the last --error-horizon-windows "
+                                   "windows whose class counts against the availability budget.", ("service",))
+        self.error_burn = r.gauge("llm_slo_agent_error_burn_rate",
+                                  "Availability budget multiples the service spends over a burn-rate pair's long or "
+                                  "short window.", ("service", "pair", "window"))
+        self.error_firing = r.gauge("llm_slo_agent_error_burn_firing",
+                                    "1 while both windows of the burn-rate pair burn at its factor or more.",
+                                    ("service", "pair"))
+        self.error_events = r.counter("llm_slo_agent_error_events_total",
+                                      "Error SLI events: out_of_group (a group beyond the window's), reserved (an "
+                                      "outcome class of 8-15, which nothing writes).", ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -396,6 +412,34 @@ class AgentMetrics:
                 self.drift_ratio.set(float(s["shift_ratio"]), name)
         for reason in EVENT_STATS:
             self.drift_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_errors(self, res: dict, stats: dict, names, pairs, budget_ppm: int, bad_mask: int) -> None:
+        """One window of the error SLI tracker: ``res`` carries the err_* arrays per group
+        (pipeline/errsli.py RESULT_KEYS), ``stats`` by name; ``pairs`` as (long windows, short windows,
+        factor_milli)."""
+        from ..pipeline.errsli import CLASSES, EVENT_STATS, burn_rate
+
+        roll = np.asarray(res["err_counts_roll"], dtype=np.int64)
+        sums = np.asarray(res["err_pair_sums"], dtype=np.int64)
+        firing = np.asarray(res["err_firing"], dtype=np.int64)
+        bad_cols = [j for j in range(len(CLASSES)) if (bad_mask >> j) & 1]
+        for g, counts in enumerate(np.asarray(res["err_counts"], dtype=np.int64).tolist()):
+            name = names[g] if g < len(names) else f"group-{g}"
+            for outcome, n in zip(CLASSES, counts):
+                if n:
+                    self.outcomes.inc(float(n), name, outcome)
+            n_roll = int(roll[g].sum())
+            if n_roll:  # a service without a request keeps its last value
+                self.error_ratio.set(float(roll[g, bad_cols].sum()) / n_roll, name)
+            for p, (L, S, f) in enumerate(pairs):
+                label = f"{L}:{S}:{f / 1000.0:g}"
+                for k, window in enumerate(("long", "short")):
+                    b = burn_rate(int(sums[g, p, 2 * k]), int(sums[g, p, 2 * k + 1]), budget_ppm)
+                    if b is not None:
+                        self.error_burn.set(b, name, label, window)
+                self.error_firing.set(float((int(firing[g]) >> p) & 1), name, label)
+        for reason in EVENT_STATS:
+            self.error_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

@@ -96,6 +96,11 @@ class WorkerSpec:
     ttft_drift: Optional[Tuple[int, int, int]] = None  # (R, L, B) of the TTFT drift tracker (agent --ttft-drift); None: off
     drift_crit: float = 4.0     # c^2 (agent --drift-crit)
     drift_min_shift: int = 2    # s, buckets (agent --drift-min-shift-buckets)
+    error_sli: int = 0          # windows of the error SLI's rolling horizon (agent --error-sli); 0: off
+    error_target: float = 0.999  # the availability target (agent --error-slo-target)
+    error_pairs: Optional[Tuple[Tuple[int, int, int], ...]] = None  # (long, short, factor_milli) in windows
+    error_min_requests: int = 20  # agent --error-min-requests
+    error_bad_mask: int = 0xF8  # the classes that burn the budget (agent --error-bad-classes)
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
@@ -105,6 +110,8 @@ DECODE_RESULT_KEYS = ("decode_cells", "decode_cells_roll", "decode_sum_ms", "dec
 # the TTFT drift's (pipeline/drift.py RESULT_KEYS)
 DRIFT_RESULT_KEYS = ("drift_state", "drift_hold", "drift_n_win", "drift_n_recent", "drift_n_base", "drift_base_fill",
                      "drift_slow_num", "drift_fast_num", "drift_q_recent", "drift_q_base")
+# the error SLI's (pipeline/errsli.py RESULT_KEYS)
+ERROR_RESULT_KEYS = ("err_counts", "err_counts_roll", "err_pair_sums", "err_firing", "err_age")
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -120,7 +127,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
                 "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS,
-                *DRIFT_RESULT_KEYS):
+                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -196,7 +203,10 @@ class WorkerCore:
                                    onset_bin_ns=spec.onset_bin_ns, onset_ref_ppm=spec.onset_ref_ppm,
                                    onset_alarm=spec.onset_alarm, decode_sli=spec.decode_sli,
                                    tpot_slo_ms=spec.tpot_slo_ms, ttft_drift=spec.ttft_drift,
-                                   drift_crit=spec.drift_crit, drift_min_shift=spec.drift_min_shift)
+                                   drift_crit=spec.drift_crit, drift_min_shift=spec.drift_min_shift,
+                                   error_sli=spec.error_sli, error_target=spec.error_target,
+                                   error_pairs=spec.error_pairs, error_min_requests=spec.error_min_requests,
+                                   error_bad_mask=spec.error_bad_mask)
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -378,6 +388,10 @@ class WorkerCore:
                 from ..pipeline.drift import stats_dict as drift_stats
 
                 d["ttft_drift"] = drift_stats(pipe.drift_results(k, n_groups)["stats"])
+            if pipe.errors is not None:  # the error SLI tracker's statistics of the window
+                from ..pipeline.errsli import stats_dict as error_stats
+
+                d["error_sli"] = error_stats(pipe.error_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

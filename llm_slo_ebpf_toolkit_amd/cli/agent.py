@@ -172,6 +172,26 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         ("drift-crit", d.drift_crit, "--ttft-drift: c^2, the critical value of D^2 n_e (reasoned, untuned)"),
         ("drift-min-shift-buckets", d.drift_min_shift_buckets, "--ttft-drift: buckets (1/16 octave each) p50 or p90 "
                                                                "must have moved (untuned: 2 is about 6 percent)"),
+        ("error-sli", False, "gpu engine: per service, the finished requests by the outcome class their spans carry "
+                             "(HTTP / gRPC status, error.type, span status: ok, client, cancelled, throttled, timeout, "
+                             "unavailable, server, other) of the window and of a rolling horizon, and a multi-window, "
+                             "multi-burn-rate evaluation of the availability error budget, on the GPU -- an errors "
+                             "field in the decision log, llm_slo_agent_request_outcomes_total / _error_ratio / "
+                             "_error_burn_rate / _error_burn_firing; one GPU only; the horizon is not checkpointed"),
+        ("error-slo-target", d.error_slo_target, "--error-sli: the availability target (the budget is 1 - target)"),
+        ("error-burn-pairs", d.error_burn_pairs, "--error-sli: up to four long_s:short_s:factor, comma separated; a pair "
+                                                 "fires when both windows spend the budget at least factor times as fast "
+                                                 "as the target allows (the SRE workbook's two paging pairs; reasoned, "
+                                                 "not tuned)"),
+        ("error-min-requests", d.error_min_requests, "--error-sli: fewest requests in a pair's window for it to burn "
+                                                     "(reasoned, not tuned)"),
+        ("error-bad-classes", d.error_bad_classes, "--error-sli: the classes that burn the budget, comma separated "
+                                                   "(client and cancelled are the caller's)"),
+        ("error-horizon-windows", d.error_horizon_windows, "--error-sli: windows of the rolling horizon (0 = the longest "
+                                                           "pair)"),
+        ("emit-on-error-burn", False, "--error-sli: the emission gate becomes 'burning or a burn-rate pair fires' (the "
+                                      "decision log's gate says which); a window the error gate opened that holds a "
+                                      "failure is not held back as recovered"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -233,6 +253,9 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         drift_recent_windows=int(a.drift_recent_windows), drift_gap_windows=int(a.drift_gap_windows),
         drift_baseline_windows=int(a.drift_baseline_windows), drift_crit=float(a.drift_crit),
         drift_min_shift_buckets=int(a.drift_min_shift_buckets),
+        error_sli=bool(a.error_sli), error_slo_target=float(a.error_slo_target), error_burn_pairs=str(a.error_burn_pairs),
+        error_min_requests=int(a.error_min_requests), error_bad_classes=str(a.error_bad_classes),
+        error_horizon_windows=int(a.error_horizon_windows), emit_on_error_burn=bool(a.emit_on_error_burn),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

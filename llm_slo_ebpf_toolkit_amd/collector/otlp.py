@@ -217,9 +217,33 @@ def parse_proto(body: bytes) -> List[Tuple[Dict[str, object], dict]]:
                         d["endTimeUnixNano"] = v4
                     elif f4 == 9:
                         attrs.append(v4)
+                    elif f4 == 15 and _w4 == 2:  # Status: 2 the message, 3 the code
+                        for f5, w5, v5 in _fields(v4):
+                            if f5 == 3 and w5 == 0:
+                                d["statusCode"] = int(v5)
                 d["attrs"] = _attrs_pb(attrs)
                 out.append((res_attrs, d))
     return out
+
+
+_STATUS_NAMES = {"STATUS_CODE_UNSET": 0, "STATUS_CODE_OK": 1, "STATUS_CODE_ERROR": 2}
+
+
+def _status_code(v) -> int:
+    """OTLP/JSON ``status.code``: an integer, or the enum's name; anything else is UNSET."""
+    if isinstance(v, str):
+        if v in _STATUS_NAMES:
+            return _STATUS_NAMES[v]
+        try:
+            return int(v)
+        except ValueError:
+            return 0
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        return 0
+    try:
+        return int(v)
+    except (ValueError, OverflowError):
+        return 0
 
 
 def _json_value(v: dict):
@@ -249,6 +273,9 @@ def parse_json(body: bytes) -> List[Tuple[Dict[str, object], dict]]:
             for sp in ss.get("spans", []) or []:
                 d = dict(sp)
                 d["attrs"] = _attrs_json(sp.get("attributes"))
+                st = sp.get("status")
+                if isinstance(st, dict) and st.get("code") is not None:
+                    d["statusCode"] = _status_code(st.get("code"))
                 out.append((res_attrs, d))
     return out
 
@@ -321,20 +348,77 @@ def tpot_us(attrs: Dict[str, object], ttft_ms: float, latency_ms: float) -> int:
     return 0
 
 
+def _number(v) -> Optional[int]:
+    """A status code attribute as an integer; ``None`` for what is no whole number."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, str)):
+        return None
+    try:
+        x = float(v)
+    except (TypeError, ValueError):
+        return None
+    if not np.isfinite(x) or x != int(x):
+        return None
+    return int(x)
+
+
+_HTTP_CLASS = {429: records.OUTCOME_THROTTLED, 408: records.OUTCOME_TIMEOUT, 504: records.OUTCOME_TIMEOUT,
+               499: records.OUTCOME_CANCELLED, 502: records.OUTCOME_UNAVAILABLE, 503: records.OUTCOME_UNAVAILABLE}
+_GRPC_CLASS = {1: records.OUTCOME_CANCELLED, 4: records.OUTCOME_TIMEOUT, 8: records.OUTCOME_THROTTLED,
+               14: records.OUTCOME_UNAVAILABLE,
+               **{c: records.OUTCOME_SERVER for c in (2, 10, 12, 13, 15)},
+               **{c: records.OUTCOME_CLIENT for c in (3, 5, 6, 7, 9, 11, 16)}}
+
+
+def outcome_class(attrs: Dict[str, object], status_code: object = None) -> int:
+    """A finished request's outcome class (records.OUTCOME_*, 0 = ok). The first source that yields a
+    non-zero class decides: the HTTP status (``http.response.status_code``, else ``http.status_code``);
+    ``rpc.grpc.status_code``; ``error.type``; the span status ERROR or a truthy ``llm.slo.error``. A value
+    that is not a number where one is expected yields nothing."""
+    h = attrs.get("http.response.status_code")
+    if h is None:
+        h = attrs.get("http.status_code")
+    h = _number(h)
+    if h is not None and h >= 400:
+        c = _HTTP_CLASS.get(h)
+        if c is None:
+            c = records.OUTCOME_SERVER if 500 <= h <= 599 else (records.OUTCOME_CLIENT if h <= 499 else 0)
+        if c:
+            return c
+    c = _GRPC_CLASS.get(_number(attrs.get("rpc.grpc.status_code")), 0)
+    if c:
+        return c
+    e = attrs.get("error.type")
+    if isinstance(e, str) and e:
+        e = e.lower()
+        if "cancel" in e:
+            return records.OUTCOME_CANCELLED
+        if "timeout" in e or "deadline" in e:
+            return records.OUTCOME_TIMEOUT
+        if "throttl" in e or "rate_limit" in e or "ratelimit" in e:
+            return records.OUTCOME_THROTTLED
+        return records.OUTCOME_OTHER
+    if _number(status_code) == 2 or _truthy(attrs.get(semconv.ATTR_SLO_ERROR)):
+        return records.OUTCOME_OTHER
+    return records.OUTCOME_OK
+
+
 class SpanMapper:
     """OTLP spans -> SPAN records on the agent's ids."""
 
     def __init__(self, groups: GroupTable, pod_id: Callable[[str], int], node_id: int = 0,
                  pod_ips: Optional[Callable[[], Dict[str, set]]] = None, forwarders: str = "",
-                 decode_sli: bool = False):
+                 decode_sli: bool = False, error_sli: bool = False):
         """``pod_ips()`` -> {IP: pod uids at that IP} of this node's pods (procfs.pod_addresses):
         a span that names a pod is kept only when it comes from that pod's address (or from an
         address the map does not know). ``forwarders``: CIDRs of trusted span forwarders (an
         OpenTelemetry collector relaying many pods' spans) the address check does not apply to.
         ``decode_sli``: a request span's time per output token goes into bits 8-31 of its ``flags``
-        (``tpot_us``); off, the records are what they were."""
+        (``tpot_us``); off, the records are what they were. ``error_sli``: the record that ends a request
+        gets the request's outcome class in bits 4-7 of its ``flags`` (``outcome_class``), with or without
+        a TTFT; off, the records are what they were."""
         self.groups, self.pod_id, self.node_id = groups, pod_id, node_id
         self.decode_sli = bool(decode_sli)
+        self.error_sli = bool(error_sli)
         self.pod_ips = pod_ips
         self.forwarders = [ipaddress.ip_network(c.strip(), strict=False) for c in forwarders.split(",") if c.strip()]
         self.conflicts = 0  # spans that named a pod already bound to another service (dropped)
@@ -501,6 +585,10 @@ class SpanMapper:
             # or first-token record (one without a trace id carries no flag, but is no request span either)
             if self.decode_sli and not start and v is not None and not _truthy(a.get(semconv.ATTR_SLO_TTFT_EARLY)):
                 fl |= records.pack_tpot_us(tpot_us(a, float(v), (t1 - t0) / 1e6))
+            # the outcome rides on the record that ends the request too, but needs no TTFT: a failed
+            # request usually has none
+            if self.error_sli and not (fl & (records.SPAN_START | records.SPAN_FIRST_TOKEN)):
+                fl |= records.pack_outcome(outcome_class(a, d.get("statusCode")))
             flags.append(fl)
             # the trace's retrieval breakdown goes to its first record (a first-token record when the
             # service exports one), once: later records of the trace carry only what arrives with them

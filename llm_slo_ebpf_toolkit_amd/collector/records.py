@@ -236,7 +236,8 @@ SPAN = np.dtype([
     # request's kernel evidence reaches the window its SLI is counted in; bit 3 (SPAN_START): a start
     # record (llm.slo.request_start: "this request started at ts_ns", ttft_ms NaN, always with
     # SPAN_NO_SLI) -- joins, never counts; the open-request tracker (pipeline/openreq.py) reads it;
-    # bits 4-7 free; bits 8-31 (SPAN_TPOT_SHIFT): the request's time per output token in integer
+    # bits 4-7 (SPAN_OUTCOME_MASK): the request's outcome class, 0 = ok (collector/otlp.py error_sli;
+    # pipeline/errsli.py reads it); bits 8-31 (SPAN_TPOT_SHIFT): the request's time per output token in integer
     # microseconds, 0 = no decode SLI (collector/otlp.py decode_sli; pipeline/decodesli.py reads it).
     # Every other reader tests the flag bits by mask
     ("flags", "<u4"),
@@ -245,7 +246,30 @@ SPAN_LATE, SPAN_NO_SLI, SPAN_FIRST_TOKEN = 1, 2, 4
 SPAN_START = 8
 SPAN_TPOT_SHIFT = 8
 SPAN_TPOT_MAX = (1 << 24) - 1
+SPAN_OUTCOME_SHIFT = 4
+SPAN_OUTCOME_MASK = 0xF0
+# the outcome classes (pipeline/errsli.py CLASSES); 8-15 are reserved and never written
+OUTCOME_OK, OUTCOME_CLIENT, OUTCOME_CANCELLED, OUTCOME_THROTTLED = 0, 1, 2, 3
+OUTCOME_TIMEOUT, OUTCOME_UNAVAILABLE, OUTCOME_SERVER, OUTCOME_OTHER = 4, 5, 6, 7
 assert SPAN.itemsize == 64
+
+
+def span_outcome(flags):
+    """The outcome class (0..15) a record's ``flags`` carry; scalars and arrays alike."""
+    if isinstance(flags, np.ndarray):
+        return (flags.astype(np.uint32) >> np.uint32(SPAN_OUTCOME_SHIFT)) & np.uint32(15)
+    return (int(flags) >> SPAN_OUTCOME_SHIFT) & 15
+
+
+def pack_outcome(c):
+    """The class ``c`` (0..15) as the bits to OR into ``flags``; scalars and arrays alike."""
+    if isinstance(c, np.ndarray):
+        if len(c) and (c.min() < 0 or c.max() > 15):
+            raise ValueError("an outcome class must be in [0, 15]")
+        return c.astype(np.uint32) << np.uint32(SPAN_OUTCOME_SHIFT)
+    if not 0 <= int(c) <= 15:
+        raise ValueError("an outcome class must be in [0, 15]")
+    return int(c) << SPAN_OUTCOME_SHIFT
 
 
 def span_tpot_us(flags):

@@ -24,6 +24,8 @@ ATTR_SLO_TOKENS_PER_SEC = "llm.slo.tokens_per_sec"
 # the request's time per output token after the first, ms (the decode-phase SLI; collector/otlp.py
 # derives it from tokens_per_sec or the output token count where a service does not set it)
 ATTR_SLO_TPOT_MS = "llm.slo.tpot_ms"
+# truthy: the request failed, cause unknown (the error SLI's class `other`; collector/otlp.py outcome_class)
+ATTR_SLO_ERROR = "llm.slo.error"
 ATTR_RETRIEVAL_VECTORDB = "llm.slo.retrieval.vectordb_ms"
 ATTR_RETRIEVAL_NETWORK_MS = "llm.slo.retrieval.network_ms"
 ATTR_RETRIEVAL_DNS_MS = "llm.slo.retrieval.dns_ms"

@@ -205,12 +205,15 @@ class SpanExporter:
         return {"stringValue": str(v)}
 
     @staticmethod
-    def span(trace_id: str, span_id: str, parent: str, name: str, t0: int, t1: int, attrs: Dict[str, object]):
+    def span(trace_id: str, span_id: str, parent: str, name: str, t0: int, t1: int, attrs: Dict[str, object],
+             error: bool = False):
         d = {"traceId": trace_id, "spanId": span_id, "name": name, "kind": 2, "startTimeUnixNano": str(t0),
              "endTimeUnixNano": str(t1),
              "attributes": [{"key": k, "value": SpanExporter._val(v)} for k, v in attrs.items()]}
         if parent:
             d["parentSpanId"] = parent
+        if error:
+            d["status"] = {"code": "STATUS_CODE_ERROR"}
         return d
 
     def add(self, spans: List[dict], urgent: bool = False) -> None:
@@ -343,6 +346,9 @@ class RagService:
                                 ("tier", "enriched"))
         self.m_burn = r.gauge("llm_slo_burn_rate", "Error-budget burn rate (5 min window, 99% objective).")
 
+    # what a request whose generation failed is answered with, and what its request span says
+    FAIL_STATUS = 500
+
     def _fail(self, profile: str) -> None:
         self.m_req.inc(1, "error", profile)
         self.m_err.inc(1, profile)
@@ -423,6 +429,10 @@ class RagService:
             g = self.backend.generate(prompt, max_tokens, seed, plan, on_tok, on_start=on_start)
         except Exception:
             self._fail(profile)
+            # the request ends here: its span says how (no TTFT: the agent's error SLI needs none)
+            self.spans.add([SpanExporter.span(trace_id, root, "", "chat.request", t_req, time.time_ns(), {
+                "request.id": rid, "llm.profile": profile, "llm.seed": seed, "llm.backend": self.backend.name,
+                "http.response.status_code": self.FAIL_STATUS}, error=True)])
             raise
         finally:
             self.gpu_tag.set("")
@@ -439,7 +449,8 @@ class RagService:
         self.m_req.inc(1, "ok", profile)
         self.m_burn.set(self.burn.observe(True))
         root_attrs = {"request.id": rid, "llm.profile": profile, "llm.seed": seed, "llm.backend": self.backend.name,
-                      semconv.ATTR_SLO_TTFT_MS: ttft_ms, semconv.ATTR_SLO_TOKENS_PER_SEC: tps}
+                      semconv.ATTR_SLO_TTFT_MS: ttft_ms, semconv.ATTR_SLO_TOKENS_PER_SEC: tps,
+                      "http.response.status_code": 200}
         root_attrs.update({k: float(v) for k, v in (attrs or {}).items()})
         root_attrs.update(conn_attrs)
         if decision.tier:
@@ -514,7 +525,7 @@ class RagService:
                 except ValueError as exc:
                     self._json(400, {"error": str(exc)})
                 except Exception as exc:  # noqa: BLE001
-                    self._json(502, {"error": f"generation failed: {exc}"})
+                    self._json(svc.FAIL_STATUS, {"error": f"generation failed: {exc}"})
 
         return H
 

@@ -142,7 +142,8 @@ def main(argv=None) -> int:
         stats["requests"] += 1
         spans.add([SpanExporter.span(trace, root, "", "chat.request", t0, t1, {
             "request.id": rid, "llm.tp.world_size": world, semconv.ATTR_SLO_TTFT_MS: r["ttft_ms"],
-            semconv.ATTR_SLO_TOKENS_PER_SEC: r["tokens_per_s"], "llm.queue_ms": round((t0 - t_arrive) / 1e6, 3)})])
+            semconv.ATTR_SLO_TOKENS_PER_SEC: r["tokens_per_s"], "llm.queue_ms": round((t0 - t_arrive) / 1e6, 3),
+            "http.response.status_code": 200})])
         return {"request_id": rid, "trace_id": trace, "ttft_ms": round(r["ttft_ms"], 3),
                 "tokens_per_sec": round(r["tokens_per_s"], 3), "tokens": [VOCAB[i % len(VOCAB)] for i in range(max_new)]}
 

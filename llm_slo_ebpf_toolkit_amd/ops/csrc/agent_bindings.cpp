@@ -12,6 +12,7 @@
 #include "decodesli.h"
 #include "drift.h"
 #include "engine.h"
+#include "errsli.h"
 #include "exemplars.h"
 #include "onset.h"
 #include "openreq.h"
@@ -949,6 +950,119 @@ class PyDriftTracker {
   std::unique_ptr<DriftTracker> t_;
 };
 
+// The error SLI tracker (errsli.h): one step per window over the same span ranges the engine gets;
+// results per step index (pipeline/errsli.py RESULT_FIELDS).
+errsli::Config errsli_config(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double target,
+                             const std::vector<std::tuple<int64_t, int64_t, int64_t>>& pairs, int64_t min_requests,
+                             int64_t bad_mask, bool lds) {
+  if (span_cap < 1) throw std::invalid_argument("error sli: span_cap must be >= 1");
+  if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("error sli: the horizon needs more than 2 GiB");
+  if (bad_mask < 0 || bad_mask > 0xffffffffll) throw std::invalid_argument("error sli: bad_mask must be non-zero and within 0xFE");
+  errsli::Config c;
+  c.device = device;
+  c.span_cap = (int)span_cap;
+  c.group_cap = group_cap;
+  c.windows = windows;
+  c.n_buffers = n_buffers;
+  c.target = target;
+  c.pairs.clear();
+  for (const auto& p : pairs) {
+    const int64_t l = std::get<0>(p), s = std::get<1>(p);
+    if (l < 1 || l > (int64_t(1) << 30) || s < 1 || s > (int64_t(1) << 30))
+      throw std::invalid_argument("error sli: a pair needs 1 <= short <= long <= windows");
+    c.pairs.push_back(errsli::Pair{(int)l, (int)s, std::get<2>(p)});
+  }
+  c.min_requests = min_requests;
+  c.bad_mask = (uint32_t)bad_mask;
+  c.lds = lds;
+  errsli::validate(c);
+  return c;
+}
+
+class PyErrorSliTracker {
+ public:
+  PyErrorSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double target,
+                    const std::vector<std::tuple<int64_t, int64_t, int64_t>>& pairs, int64_t min_requests, int64_t bad_mask,
+                    bool lds) {
+    t_ = std::make_unique<ErrorSliTracker>(
+        errsli_config(device, span_cap, group_cap, windows, n_buffers, target, pairs, min_requests, bad_mask, lds));
+  }
+  ErrorSliTracker& t() {
+    if (!t_) throw std::logic_error("error sli closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    ErrorSliTracker& es = t();
+    py::gil_scoped_release nogil;
+    return es.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  uint32_t budget_ppm() { return t().budget_ppm(); }
+  // the whole result block of step i as it left the device (uint32 words)
+  py::array_t<uint32_t> block(int64_t i) {
+    ErrorSliTracker& es = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = es.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)es.result_layout().words});
+  }
+  py::dict results(int64_t i, int n_groups) {
+    ErrorSliTracker& es = t();
+    if (n_groups < 0 || n_groups > es.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = es.results(i);
+    }
+    const errsli::Layout& l = es.result_layout();
+    const py::ssize_t G = n_groups;
+    py::dict d;
+    d["counts"] = copy_array(r + l.counts, {G, errsli::kClasses});
+    d["counts_roll"] = copy_array(r + l.counts_roll, {G, errsli::kClasses});
+    d["pair_sums"] = copy_array(r + l.pair_sums, {G, errsli::kMaxPairs, errsli::kPairWords});
+    d["firing"] = copy_array(r + l.firing, {G});
+    d["age"] = copy_array(r + l.age, {G});
+    d["stats"] = copy_array(r + l.stats, {errsli::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (rolling counts u32 [group_cap, 8], pair sums u32 [group_cap, 4, 4], ages u32 [group_cap], ring position)
+  py::tuple resident() {
+    ErrorSliTracker& es = t();
+    errsli::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = es.resident();
+    }
+    const py::ssize_t G = es.config().group_cap;
+    return py::make_tuple(copy_array(h.counts.data(), {G, errsli::kClasses}),
+                          copy_array(h.sums.data(), {G, errsli::kMaxPairs, errsli::kPairWords}),
+                          copy_array(h.age.data(), {G}), h.pos);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<ErrorSliTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -1127,6 +1241,46 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyDriftTracker::resident)
       .def("sync", &PyDriftTracker::sync)
       .def("close", &PyDriftTracker::close);
+  m.attr("ERRSLI_CLASSES") = errsli::kClasses;
+  m.attr("ERRSLI_MAX_PAIRS") = errsli::kMaxPairs;
+  m.attr("ERRSLI_STATS") = (int)errsli::kStats;
+  m.attr("ERRSLI_LDS_SLOTS") = errsli::kLdsSlots;
+  m.attr("ERRSLI_BAD_DEFAULT") = errsli::kBadDefault;
+  m.def("errsli_outcome_of", [](uint32_t flags) { return errsli::outcome_of(flags); });
+  m.def("errsli_pack_outcome", [](uint32_t c) { return errsli::pack_outcome(c); });
+  m.def("errsli_budget_ppm", [](double target) { return errsli::budget_ppm(target); });
+  m.def("errsli_burns", [](uint32_t n, uint32_t bad, uint32_t min_requests, uint64_t thr) {
+    return errsli::burns(n, bad, min_requests, thr);
+  });
+  m.def("errsli_next_age", [](uint32_t age, uint32_t firing) { return errsli::next_age(age, firing); });
+  m.def("errsli_layout", [](int group_cap) {
+    const errsli::Layout l = errsli::layout(group_cap);
+    py::dict d;
+    d["counts"] = l.counts, d["counts_roll"] = l.counts_roll, d["pair_sums"] = l.pair_sums, d["firing"] = l.firing;
+    d["age"] = l.age, d["stats"] = l.stats, d["words"] = l.words;
+    return d;
+  });
+  m.def("errsli_device_bytes", [](int64_t span_cap, int group_cap, int windows) {
+    errsli::Config c;
+    c.span_cap = (int)span_cap, c.group_cap = group_cap, c.windows = windows;
+    return errsli::device_bytes(c);
+  });
+  py::class_<PyErrorSliTracker>(m, "ErrorSliTracker")
+      .def(py::init<int, int64_t, int, int, int, double, const std::vector<std::tuple<int64_t, int64_t, int64_t>>&, int64_t,
+                    int64_t, bool>(),
+           py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 3600,
+           py::arg("n_buffers") = 3, py::arg("target") = 0.999,
+           py::arg("pairs") = std::vector<std::tuple<int64_t, int64_t, int64_t>>{{3600, 300, 14400}},
+           py::arg("min_requests") = 20, py::arg("bad_mask") = (int64_t)errsli::kBadDefault, py::arg("lds") = true)
+      .def("step", &PyErrorSliTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyErrorSliTracker::query)
+      .def("budget_ppm", &PyErrorSliTracker::budget_ppm)
+      .def("results", &PyErrorSliTracker::results)
+      .def("block", &PyErrorSliTracker::block)
+      .def("step_ms", &PyErrorSliTracker::step_ms)
+      .def("resident", &PyErrorSliTracker::resident)
+      .def("sync", &PyErrorSliTracker::sync)
+      .def("close", &PyErrorSliTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

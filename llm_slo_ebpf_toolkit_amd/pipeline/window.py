@@ -103,7 +103,9 @@ class WindowPipeline:
                  ttft_drift: Optional[Tuple[int, int, int]] = None, drift_crit: Optional[float] = None,
                  drift_min_shift: Optional[int] = None, drift_min_recent: Optional[int] = None,
                  drift_min_base: Optional[int] = None, drift_min_base_windows: Optional[int] = None,
-                 drift_hold_max: Optional[int] = None):
+                 drift_hold_max: Optional[int] = None, error_sli: int = 0, error_target: float = 0.999,
+                 error_pairs: Optional[Sequence[Tuple[int, int, int]]] = None, error_min_requests: int = 20,
+                 error_bad_mask: int = 0xF8):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -151,7 +153,15 @@ class WindowPipeline:
         ``drift_min_base_windows`` are what a decision needs, ``drift_hold_max`` the consecutive slow windows
         after which the baseline is dropped (``None``: pipeline/drift.py's defaults; the device tracker for
         "gpu", the host oracle for "cpu"); ``results()`` then also carries the ``drift_*`` keys
-        (drift.RESULT_KEYS). ``None``: off, nothing is constructed. One GPU only."""
+        (drift.RESULT_KEYS). ``None``: off, nothing is constructed. One GPU only.
+        ``error_sli`` > 0: per service, count the finished requests by the outcome class their spans carry
+        (records.span_outcome), for every window and for a rolling horizon of that many windows, and decide
+        every window which of the ``error_pairs`` -- (long windows, short windows, factor_milli), 1 to 4;
+        ``None``: one pair over the horizon -- spend the error budget of ``error_target`` faster than their
+        factor allows, over windows of at least ``error_min_requests`` requests, with the classes of
+        ``error_bad_mask`` counted against it (pipeline/errsli.py; the device tracker for "gpu", the host
+        oracle for "cpu"); ``results()`` then also carries the ``err_*`` keys (errsli.RESULT_KEYS). 0: off,
+        nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -323,9 +333,27 @@ class WindowPipeline:
                 from .drift import DriftOracle
 
                 self.drift = DriftOracle(**fkw)
+        self.errors = None
+        self._err: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if error_sli:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the error SLI runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            W_ = int(error_sli)
+            ekw = dict(span_cap=span_cap, group_cap=group_cap, windows=W_, n_buffers=self.nb, target=float(error_target),
+                       pairs=[tuple(p) for p in error_pairs] if error_pairs is not None else [(W_, max(1, W_ // 12), 14400)],
+                       min_requests=int(error_min_requests), bad_mask=int(error_bad_mask), device=device)
+            if engine == "gpu":
+                from ..ops.errsli import ErrorSliTracker
+
+                self.errors = ErrorSliTracker(**ekw)
+            else:
+                from .errsli import ErrorSliOracle
+
+                self.errors = ErrorSliOracle(**ekw)
         # the side trackers are fixed from here on: copy_ahead asks once per window and half
         self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
-                                                        self.decode, self.drift))
+                                                        self.decode, self.drift, self.errors))
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -473,6 +501,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(drift_keys(self.drift_results(k, n_groups)))
+        if self.errors is not None:
+            from .errsli import result_keys as error_keys
+
+            res = dict(res)
+            res.update(error_keys(self.error_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -611,9 +644,29 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- error SLI (pipeline/errsli.py) -----------------------------------------------------
+    def track_errors(self, spans, n_groups: int) -> None:
+        """The error SLI tracker's step for the window about to be submitted: the same span ranges.
+        Every window steps (the horizon and the burn windows are counted in windows)."""
+        if self.errors is None:
+            return
+        self._err[self.k % self.nb] = (self.k, self.errors.step(list(spans), int(n_groups)))
+
+    def error_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The error SLI tracker's results of window k (pipeline/errsli.py RESULT_FIELDS; an empty
+        step's for a window that was submitted past ``track_errors``)."""
+        held = self._err.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.errors.results(held[1], n_groups)
+        from .errsli import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.errors is not None:
+            self.errors.close()
         if self.drift is not None:
             self.drift.close()
         if self.decode is not None:
@@ -676,6 +729,8 @@ class WindowPipeline:
             self.decode.sync()
         if self.drift is not None:
             self.drift.sync()
+        if self.errors is not None:
+            self.errors.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -999,6 +1054,8 @@ class RingWindowSource:
             pipe.track_decode(spans, n_groups)
         if pipe.drift is not None:  # the TTFT drift sees the window's spans
             pipe.track_drift(spans, n_groups)
+        if pipe.errors is not None:  # the error SLI sees the window's spans
+            pipe.track_errors(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
