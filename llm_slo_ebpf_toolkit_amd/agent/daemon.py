@@ -262,6 +262,19 @@ class AgentOptions:
     error_bad_classes: str = "throttled,timeout,unavailable,server,other"  # client and cancelled are the caller's
     error_horizon_windows: int = 0       # windows of the rolling horizon (0: the longest pair)
     emit_on_error_burn: bool = False     # needs error_sli: the emission gate becomes "burning or a pair fires"
+    # per service, traffic and saturation: arrivals, completions, requests in flight and the exact busy time over a
+    # ring of time bins on the GPU, from the start and the duration every finishing record carries, and whether the
+    # recent bins show a surge, a slowdown or a drop against the bins before them (pipeline/loadsli.py,
+    # docs/LOAD_SLI.md): a load field in the decision log and four series; one GPU; nothing is checkpointed (warming
+    # after a restart). The defaults are reasoned, not tuned
+    load_sli: bool = False
+    load_bin_ms: float = 0.0             # a bin's length (0: window_ms / 4, at least 1 ms)
+    load_bins: int = 1024                # bins of the ring per service (a power of two in 64..8192)
+    load_settle_ms: float = 15000.0      # the newest bins left out: a request still in flight is invisible (a long generation)
+    load_recent_ms: float = 15000.0      # the range compared with the bins before it
+    load_factor: float = 1.5             # the ratio that counts as up or down (the smallest clearly not window-to-window noise)
+    load_min_requests: int = 20          # fewest recent arrivals for a surge, and a base rate of as many for a drop
+    load_min_concurrency: float = 1.0    # least recent concurrency for a slowdown
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -814,6 +827,8 @@ class Agent:
                        and g < len(res["drift_state"]) else {}),
                     **({"errors": self._error_entry(res, g)} if res.get("err_counts") is not None
                        and g < len(res["err_counts"]) else {}),
+                    **({"load": self._load_entry(res, g)} if res.get("load_rows") is not None
+                       and g < len(res["load_rows"]) else {}),
                     **({"gate": "burn" if burning else ("errors" if erring else "drift")}
                        if emit and (drift_on or err_on) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
@@ -945,6 +960,50 @@ class Agent:
 
         return summary(res, g, self.error_pairs(), budget_ppm(float(self.o.error_slo_target)), self.error_bad_mask())
 
+    def load_params(self) -> dict:
+        """The load SLI tracker's parameters from the flags: a bin is --load-bin-ms or a quarter of the window,
+        1 ms at least; the millisecond flags become bins by ceil; the base needs twice the recent bins."""
+        p = getattr(self, "_load_params", None)
+        if p is None:
+            o = self.o
+            ms = float(o.load_bin_ms)
+            bin_us = max(1000, int(round((ms if ms > 0 else float(o.window_ms) / 4.0) * 1e3)))
+            recent = max(1, math.ceil(float(o.load_recent_ms) * 1e3 / bin_us))
+            p = self._load_params = dict(
+                bin_us=bin_us, settle_bins=max(0, math.ceil(float(o.load_settle_ms) * 1e3 / bin_us)), recent_bins=recent,
+                min_base_bins=2 * recent, factor_milli=int(round(float(o.load_factor) * 1000.0)),
+                min_requests=int(o.load_min_requests), min_conc_milli=int(round(float(o.load_min_concurrency) * 1000.0)))
+        return dict(p)
+
+    def check_load_flags(self) -> None:
+        """Refuse, by flag name, a --load-* combination the tracker would not take."""
+        from ..pipeline.loadsli import check_config, default_ring_records_max
+
+        o, p = self.o, self.load_params()
+        if not (math.isfinite(float(o.load_settle_ms)) and float(o.load_settle_ms) >= 0
+                and math.isfinite(float(o.load_recent_ms)) and float(o.load_recent_ms) > 0):
+            raise ValueError("--load-settle-ms must be >= 0 and --load-recent-ms > 0")
+        B = int(o.load_bins)
+        if B >= 64 and not B & (B - 1) and p["settle_bins"] + p["recent_bins"] + p["min_base_bins"] > B:
+            raise ValueError(f"--load-settle-ms {o.load_settle_ms:g} ({p['settle_bins']} bins) + --load-recent-ms "
+                             f"{o.load_recent_ms:g} ({p['recent_bins']} bins) + a base of twice the recent bins do not fit "
+                             f"--load-bins {B} at --load-bin-ms {p['bin_us'] / 1000.0:g}")
+        try:
+            check_config(B, p["bin_us"], p["settle_bins"], p["recent_bins"], p["min_base_bins"], p["factor_milli"],
+                         p["min_requests"], p["min_conc_milli"], max(1, int(o.window_spans)), max(1, int(o.window_groups)),
+                         3, default_ring_records_max(max(B, 1), p["bin_us"]))
+        except ValueError as e:
+            raise ValueError(f"{e} (--load-bins, --load-bin-ms, --load-settle-ms, --load-recent-ms, --load-factor, "
+                             "--load-min-requests, --load-min-concurrency)") from None
+
+    def _load_entry(self, res: dict, g: int) -> dict:
+        """Group g's load SLI for the decision log: the state, arrivals per second, concurrency and service time
+        of the recent and the base range, and the ring's peak; ``None`` where a denominator is 0."""
+        from ..pipeline.loadsli import summary
+
+        p = self.load_params()
+        return summary(res["load_rows"][g], p["bin_us"], p["recent_bins"])
+
     def drift_windows(self) -> Tuple[int, int, int]:
         """(R, L, B) of the TTFT drift tracker: the flags, or 10 s / 10 s / 300 s of windows."""
         from ..pipeline.drift import defaults
@@ -1046,6 +1105,9 @@ class Agent:
 
             self.metrics.observe_errors(res, head["error_sli"], names, self.error_pairs(),
                                         budget_ppm(float(self.o.error_slo_target)), self.error_bad_mask())
+        if head.get("load_sli") is not None and res.get("load_rows") is not None:
+            p = self.load_params()
+            self.metrics.observe_load(res, head["load_sli"], names, p["bin_us"], p["recent_bins"])
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -1181,6 +1243,11 @@ class Agent:
                              "the device, the error SLI tracker's are read on the host")
         if o.error_sli:  # a pair beyond the horizon's cap, an unknown class: refused here, by name
             self.error_pairs(), self.error_bad_mask()
+        if o.load_sli and N > 1:
+            raise ValueError("--load-sli runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the load SLI tracker's are read on the host")
+        if o.load_sli:  # a combination that does not fit the ring: refused here, naming the flags
+            self.check_load_flags()
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1240,7 +1307,9 @@ class Agent:
                             error_target=float(o.error_slo_target),
                             error_pairs=tuple(self.error_pairs()) if o.error_sli else None,
                             error_min_requests=int(o.error_min_requests),
-                            error_bad_mask=self.error_bad_mask() if o.error_sli else 0xF8)
+                            error_bad_mask=self.error_bad_mask() if o.error_sli else 0xF8,
+                            load_sli=int(o.load_bins) if o.load_sli else 0,
+                            load_params=tuple(sorted(self.load_params().items())) if o.load_sli else ())
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

@@ -198,6 +198,21 @@ class AgentMetrics:
         self.error_events = r.counter("llm_slo_agent_error_events_total",
                                       "Error SLI events: out_of_group (a group beyond the window's), reserved (an "
                                       "outcome class of 8-15, which nothing writes).", ("reason",))
+        # load SLI (agent --load-sli, pipeline/loadsli.py): traffic and saturation
+        self.load_state = r.gauge("llm_slo_agent_load_state",
+                                  "Load state by service: 0 steady, 1 surge (arrivals up by --load-factor), 2 slowdown "
+                                  "(concurrency up at the same arrivals), 3 drop (arrivals down), 4 warming.", ("service",))
+        self.request_rate = r.gauge("llm_slo_agent_request_rate",
+                                    "Requests per second arriving at the service over the recent range and over the "
+                                    "base range before it.", ("service", "range"))
+        self.concurrency = r.gauge("llm_slo_agent_concurrency",
+                                   "Requests in flight at the service, averaged over the recent and the base range, and "
+                                   "the ring's peak.", ("service", "range"))
+        self.load_events = r.counter("llm_slo_agent_load_events_total",
+                                     "Load SLI events: out_of_group (a group beyond the window's), invalid (a duration NaN, "
+                                     "negative or above a day), no_time, future (starting or ending ahead of the cut), "
+                                     "too_old, clipped (started before the ring), long (longer than --load-settle-ms).",
+                                     ("reason",))
         # GPU signals' value distributions (the window histograms the decode kernel builds)
         self.gpu_hist = {s.slot: r.histogram(f"llm_ebpf_{s.name}", f"{s.name} values observed from GPU signal records.",
                                              s.buckets)
@@ -440,6 +455,24 @@ class AgentMetrics:
                 self.error_firing.set(float((int(firing[g]) >> p) & 1), name, label)
         for reason in EVENT_STATS:
             self.error_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_load(self, res: dict, stats: dict, names, bin_us: int, recent_bins: int) -> None:
+        """One window of the load SLI tracker: ``res`` carries ``load_rows`` per group (pipeline/loadsli.py
+        LOAD_ROW), ``stats`` by name; a bin's length and the recent range's bins."""
+        from ..pipeline.loadsli import EVENT_STATS, summary
+
+        for g, row in enumerate(res["load_rows"]):
+            name = names[g] if g < len(names) else f"group-{g}"
+            s = summary(row, bin_us, recent_bins)
+            self.load_state.set(float(int(row["state"])), name)
+            self.concurrency.set(float(s["concurrency"]["peak"]), name, "peak")
+            for rng in ("recent", "base"):  # a warming row keeps the last values
+                if s["arrivals_per_s"][rng] is not None:
+                    self.request_rate.set(float(s["arrivals_per_s"][rng]), name, rng)
+                if s["concurrency"][rng] is not None:
+                    self.concurrency.set(float(s["concurrency"][rng]), name, rng)
+        for reason in EVENT_STATS:
+            self.load_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_attribution(self, domain: str) -> None:
         self.attr.inc(1, domain)

@@ -101,6 +101,10 @@ class WorkerSpec:
     error_pairs: Optional[Tuple[Tuple[int, int, int], ...]] = None  # (long, short, factor_milli) in windows
     error_min_requests: int = 20  # agent --error-min-requests
     error_bad_mask: int = 0xF8  # the classes that burn the budget (agent --error-bad-classes)
+    load_sli: int = 0           # bins of the load SLI's ring per service (agent --load-sli, --load-bins); 0: off
+    # its parameters as sorted (name, value) pairs: bin_us, settle_bins, recent_bins, min_base_bins, factor_milli,
+    # min_requests, min_conc_milli (agent --load-*; daemon.load_params)
+    load_params: Tuple[Tuple[str, int], ...] = ()
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
@@ -127,7 +131,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
                 "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS,
-                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS):
+                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS, "load_rows"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -206,7 +210,8 @@ class WorkerCore:
                                    drift_crit=spec.drift_crit, drift_min_shift=spec.drift_min_shift,
                                    error_sli=spec.error_sli, error_target=spec.error_target,
                                    error_pairs=spec.error_pairs, error_min_requests=spec.error_min_requests,
-                                   error_bad_mask=spec.error_bad_mask)
+                                   error_bad_mask=spec.error_bad_mask, load_sli=spec.load_sli,
+                                   **{f"load_{name}": int(v) for name, v in spec.load_params})
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -392,6 +397,10 @@ class WorkerCore:
                 from ..pipeline.errsli import stats_dict as error_stats
 
                 d["error_sli"] = error_stats(pipe.error_results(k, n_groups)["stats"])
+            if pipe.load is not None:  # the load SLI tracker's statistics of the window
+                from ..pipeline.loadsli import stats_dict as load_stats
+
+                d["load_sli"] = load_stats(pipe.load_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

@@ -192,6 +192,25 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         ("emit-on-error-burn", False, "--error-sli: the emission gate becomes 'burning or a burn-rate pair fires' (the "
                                       "decision log's gate says which); a window the error gate opened that holds a "
                                       "failure is not held back as recovered"),
+        ("load-sli", False, "gpu engine: per service, traffic and saturation -- arrivals, completions, requests in flight "
+                            "and the exact busy time over a ring of time bins on the GPU, from the start and the "
+                            "duration every finishing span carries; the recent bins against the bins before them say "
+                            "steady, surge (more arrivals), slowdown (more in flight at the same arrivals) or drop -- a "
+                            "load field in the decision log, llm_slo_agent_load_state / _request_rate / _concurrency; "
+                            "one GPU only; the ring is not checkpointed (warming after a restart)"),
+        ("load-bin-ms", d.load_bin_ms, "--load-sli: a time bin's length (0 = window-ms / 4; at least 1)"),
+        ("load-bins", d.load_bins, "--load-sli: bins of the ring per service (a power of two in 64..8192)"),
+        ("load-settle-ms", d.load_settle_ms, "--load-sli: the newest time left out -- a request still in flight is "
+                                             "invisible until it finishes (reasoned, not tuned: 15 s covers a long "
+                                             "generation)"),
+        ("load-recent-ms", d.load_recent_ms, "--load-sli: the recent range compared with the bins before it (reasoned, "
+                                             "not tuned)"),
+        ("load-factor", d.load_factor, "--load-sli: the ratio that counts as up or down, 1.001..64 (reasoned, not tuned: "
+                                       "1.5 is the smallest clearly not window-to-window noise)"),
+        ("load-min-requests", d.load_min_requests, "--load-sli: fewest recent arrivals for a surge; a drop needs a base "
+                                                   "rate of as many (reasoned, not tuned)"),
+        ("load-min-concurrency", d.load_min_concurrency, "--load-sli: least recent concurrency for a slowdown (reasoned, "
+                                                         "not tuned)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -256,6 +275,9 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         error_sli=bool(a.error_sli), error_slo_target=float(a.error_slo_target), error_burn_pairs=str(a.error_burn_pairs),
         error_min_requests=int(a.error_min_requests), error_bad_classes=str(a.error_bad_classes),
         error_horizon_windows=int(a.error_horizon_windows), emit_on_error_burn=bool(a.emit_on_error_burn),
+        load_sli=bool(a.load_sli), load_bin_ms=float(a.load_bin_ms), load_bins=int(a.load_bins),
+        load_settle_ms=float(a.load_settle_ms), load_recent_ms=float(a.load_recent_ms), load_factor=float(a.load_factor),
+        load_min_requests=int(a.load_min_requests), load_min_concurrency=float(a.load_min_concurrency),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

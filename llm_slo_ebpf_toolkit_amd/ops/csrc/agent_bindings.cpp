@@ -14,6 +14,7 @@
 #include "engine.h"
 #include "errsli.h"
 #include "exemplars.h"
+#include "loadsli.h"
 #include "onset.h"
 #include "openreq.h"
 #include "podrank.h"
@@ -1063,6 +1064,107 @@ class PyErrorSliTracker {
   std::unique_ptr<ErrorSliTracker> t_;
 };
 
+// The load SLI tracker (loadsli.h): one step per timed window cut over the same span ranges the
+// engine gets; results per step index. Rows leave as bytes [G, 80] (pipeline/loadsli.py LOAD_ROW).
+class PyLoadSliTracker {
+ public:
+  PyLoadSliTracker(int device, int64_t bins, int64_t bin_us, int64_t settle_bins, int64_t recent_bins, int64_t min_base_bins,
+                   int64_t factor_milli, int64_t min_requests, int64_t min_conc_milli, int64_t span_cap, int group_cap,
+                   int n_buffers, int64_t ring_records_max, bool lds) {
+    if (bins < loadsli::kMinBins || bins > loadsli::kMaxBins)
+      throw std::invalid_argument("load sli: bins must be a power of two in [64, 8192]");
+    if (span_cap < 1) throw std::invalid_argument("load sli: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("load sli: the ring needs more than 2 GiB");
+    auto small = [](int64_t v) { return v < -1 ? -1 : (v > (int64_t(1) << 30) ? (1 << 30) : (int)v); };
+    loadsli::Config c;
+    c.device = device;
+    c.bins = (int)bins;
+    c.bin_us = bin_us;
+    c.settle_bins = small(settle_bins);
+    c.recent_bins = small(recent_bins);
+    c.min_base_bins = small(min_base_bins);
+    c.factor_milli = factor_milli;
+    c.min_requests = min_requests;
+    c.min_conc_milli = min_conc_milli;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.ring_records_max = ring_records_max;
+    c.lds = lds;
+    loadsli::validate(c);
+    t_ = std::make_unique<LoadSliTracker>(c);
+  }
+  LoadSliTracker& t() {
+    if (!t_) throw std::logic_error("load sli closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
+    LoadSliTracker& ls = t();
+    py::gil_scoped_release nogil;
+    return ls.step(spans, cut_ns, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    LoadSliTracker& ls = t();
+    if (n_groups < 0 || n_groups > ls.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = ls.results(i);
+    }
+    const loadsli::Layout& l = ls.result_layout();
+    py::dict d;
+    d["rows"] = copy_array(reinterpret_cast<const uint8_t*>(r + l.rows), {(py::ssize_t)n_groups, loadsli::kRowBytes});
+    d["stats"] = copy_array(r + l.stats, {loadsli::kStats});
+    return d;
+  }
+  // the step's whole result block, uint32 words
+  py::array_t<uint32_t> block(int64_t i) {
+    LoadSliTracker& ls = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = ls.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)ls.result_layout().words});
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (counts u64, idle_us u64 [group_cap, bins] in slot order, carry, age, previous state, q_hi, q_first)
+  py::tuple resident() {
+    LoadSliTracker& ls = t();
+    loadsli::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = ls.resident();
+    }
+    const py::ssize_t G = ls.config().group_cap, B = ls.config().bins;
+    return py::make_tuple(copy_array(reinterpret_cast<const uint64_t*>(h.counts.data()), {G, B}),
+                          copy_array(reinterpret_cast<const uint64_t*>(h.idle_us.data()), {G, B}),
+                          copy_array(h.carry.data(), {G}), copy_array(h.age.data(), {G}),
+                          copy_array(h.prev_state.data(), {G}), h.q_hi, h.q_first);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<LoadSliTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -1281,6 +1383,56 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyErrorSliTracker::resident)
       .def("sync", &PyErrorSliTracker::sync)
       .def("close", &PyErrorSliTracker::close);
+  m.attr("LOADSLI_ROW_BYTES") = loadsli::kRowBytes;
+  m.attr("LOADSLI_STATS") = (int)loadsli::kStats;
+  m.attr("LOADSLI_LDS_SLOTS") = loadsli::kLdsSlots;
+  m.attr("LOADSLI_BINS") = py::make_tuple(loadsli::kMinBins, loadsli::kMaxBins);
+  // -1 for a latency the tracker counts as invalid
+  m.def("loadsli_dur_us", [](float latency_ms) {
+    return loadsli::latency_valid(latency_ms) ? loadsli::dur_us_of(latency_ms) : (int64_t)-1;
+  });
+  m.def("loadsli_place", [](int64_t ts_us, int64_t dur_us, int64_t bin_us, int64_t q_hi, uint32_t bins) {
+    const loadsli::Placement p = loadsli::place(ts_us, dur_us, bin_us, q_hi, bins);
+    return py::make_tuple(p.bits, p.qs, p.qe, p.idle_s, p.idle_e);
+  });
+  // (flags, state) of a row that is not warming
+  m.def("loadsli_classify", [](uint64_t busy_recent, uint64_t busy_base, uint32_t arr_recent, uint32_t arr_base,
+                               uint32_t base_bins, uint32_t recent_bins, int64_t bin_us, int64_t factor_milli,
+                               int64_t min_requests, int64_t min_conc_milli) {
+    if (base_bins < 1 || recent_bins < 1 || bin_us < 1) throw std::invalid_argument("load sli classify: empty range");
+    const loadsli::Sums s{busy_recent, busy_base, arr_recent, arr_base};
+    const uint32_t f = loadsli::predicates(s, base_bins, recent_bins, bin_us, factor_milli, min_requests, min_conc_milli);
+    return py::make_tuple(f, loadsli::state_of(f));
+  });
+  m.def("loadsli_age", [](uint32_t state, uint32_t prev_state, uint32_t prev_age) {
+    return loadsli::age_of(state, prev_state, prev_age);
+  });
+  m.def("loadsli_layout", [](int group_cap) {
+    const loadsli::Layout l = loadsli::layout(group_cap);
+    py::dict d;
+    d["rows"] = l.rows, d["stats"] = l.stats, d["words"] = l.words;
+    return d;
+  });
+  m.def("loadsli_device_bytes", [](int bins, int64_t span_cap, int group_cap) {
+    return loadsli::device_bytes(bins, (int)span_cap, group_cap);
+  });
+  m.def("loadsli_ring_records_max", [](int bins, int64_t bin_us) { return loadsli::default_ring_records_max(bins, bin_us); });
+  py::class_<PyLoadSliTracker>(m, "LoadSliTracker")
+      .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t,
+                    bool>(),
+           py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_us") = 500000, py::arg("settle_bins") = 30,
+           py::arg("recent_bins") = 30, py::arg("min_base_bins") = 60, py::arg("factor_milli") = 1500,
+           py::arg("min_requests") = 20, py::arg("min_conc_milli") = 1000, py::arg("span_cap") = 16384,
+           py::arg("group_cap") = 64, py::arg("n_buffers") = 3,
+           py::arg("ring_records_max") = loadsli::default_ring_records_max(1024, 500000), py::arg("lds") = true)
+      .def("step", &PyLoadSliTracker::step, py::arg("spans"), py::arg("cut_ns"), py::arg("n_groups"))
+      .def("query", &PyLoadSliTracker::query)
+      .def("results", &PyLoadSliTracker::results)
+      .def("block", &PyLoadSliTracker::block)
+      .def("step_ms", &PyLoadSliTracker::step_ms)
+      .def("resident", &PyLoadSliTracker::resident)
+      .def("sync", &PyLoadSliTracker::sync)
+      .def("close", &PyLoadSliTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -105,7 +105,10 @@ class WindowPipeline:
                  drift_min_base: Optional[int] = None, drift_min_base_windows: Optional[int] = None,
                  drift_hold_max: Optional[int] = None, error_sli: int = 0, error_target: float = 0.999,
                  error_pairs: Optional[Sequence[Tuple[int, int, int]]] = None, error_min_requests: int = 20,
-                 error_bad_mask: int = 0xF8):
+                 error_bad_mask: int = 0xF8, load_sli: int = 0, load_bin_us: Optional[int] = None,
+                 load_settle_bins: Optional[int] = None, load_recent_bins: Optional[int] = None,
+                 load_min_base_bins: Optional[int] = None, load_factor_milli: int = 1500, load_min_requests: int = 20,
+                 load_min_conc_milli: int = 1000):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -161,6 +164,15 @@ class WindowPipeline:
         factor allows, over windows of at least ``error_min_requests`` requests, with the classes of
         ``error_bad_mask`` counted against it (pipeline/errsli.py; the device tracker for "gpu", the host
         oracle for "cpu"); ``results()`` then also carries the ``err_*`` keys (errsli.RESULT_KEYS). 0: off,
+        nothing is constructed. One GPU only.
+        ``load_sli`` > 0: per service, keep a ring of that many absolute time bins of ``load_bin_us``
+        microseconds (default ``window_ms`` / 4) of request starts, ends and idle time from the finishing
+        records' start time and duration, and report every window the arrivals, completions and busy time of
+        the ``load_recent_bins`` bins before the newest ``load_settle_bins`` (defaults: 15 s each, in bins)
+        against the bins before them -- at least ``load_min_base_bins`` (default: twice the recent bins) --
+        as steady, surge, slowdown or drop by ``load_factor_milli``, ``load_min_requests`` and
+        ``load_min_conc_milli`` (pipeline/loadsli.py; the device tracker for "gpu", the host oracle for
+        "cpu"); ``results()`` then also carries ``load_rows`` / ``load_stats`` (loadsli.RESULT_KEYS). 0: off,
         nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
@@ -351,9 +363,33 @@ class WindowPipeline:
                 from .errsli import ErrorSliOracle
 
                 self.errors = ErrorSliOracle(**ekw)
+        self.load = None
+        self.load_skipped = 0  # cuts without a time (replay helpers): no tracker step
+        self._load: Dict[int, Tuple[int, Optional[int]]] = {}  # buffer -> (window, tracker step)
+        if load_sli:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the load SLI runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            bin_us = max(1000, int(round(window_ms * 1e3 / 4))) if load_bin_us is None else int(load_bin_us)
+            per_15s = -(-15_000_000 // max(bin_us, 1))
+            recent = per_15s if load_recent_bins is None else int(load_recent_bins)
+            lkw = dict(bins=int(load_sli), bin_us=bin_us,
+                       settle_bins=per_15s if load_settle_bins is None else int(load_settle_bins), recent_bins=recent,
+                       min_base_bins=2 * recent if load_min_base_bins is None else int(load_min_base_bins),
+                       factor_milli=int(load_factor_milli), min_requests=int(load_min_requests),
+                       min_conc_milli=int(load_min_conc_milli), span_cap=span_cap, group_cap=group_cap, n_buffers=self.nb,
+                       device=device)
+            if engine == "gpu":
+                from ..ops.loadsli import LoadSliTracker
+
+                self.load = LoadSliTracker(**lkw)
+            else:
+                from .loadsli import LoadSliOracle
+
+                self.load = LoadSliOracle(**lkw)
         # the side trackers are fixed from here on: copy_ahead asks once per window and half
         self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
-                                                        self.decode, self.drift, self.errors))
+                                                        self.decode, self.drift, self.errors, self.load))
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -506,6 +542,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(error_keys(self.error_results(k, n_groups)))
+        if self.load is not None:
+            from .loadsli import result_keys as load_keys
+
+            res = dict(res)
+            res.update(load_keys(self.load_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -662,9 +703,34 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- load SLI (pipeline/loadsli.py) -----------------------------------------------------
+    def track_load(self, spans, cut_ns: int, n_groups: int) -> None:
+        """The load SLI tracker's step for the window about to be submitted: the same span ranges and
+        the cut's time. A cut without a time is skipped and counted."""
+        if self.load is None:
+            return
+        step = None
+        if int(cut_ns) > 0:
+            step = self.load.step(list(spans), int(cut_ns), int(n_groups))
+        else:
+            self.load_skipped += 1
+        self._load[self.k % self.nb] = (self.k, step)
+
+    def load_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The load SLI tracker's results of window k (pipeline/loadsli.py RESULT_FIELDS; empty_result
+        for a window it skipped)."""
+        held = self._load.get(k % self.nb)
+        if held is not None and held[0] == k and held[1] is not None:
+            return self.load.results(held[1], n_groups)
+        from .loadsli import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.load is not None:
+            self.load.close()
         if self.errors is not None:
             self.errors.close()
         if self.drift is not None:
@@ -731,6 +797,8 @@ class WindowPipeline:
             self.drift.sync()
         if self.errors is not None:
             self.errors.sync()
+        if self.load is not None:
+            self.load.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -1056,6 +1124,8 @@ class RingWindowSource:
             pipe.track_drift(spans, n_groups)
         if pipe.errors is not None:  # the error SLI sees the window's spans
             pipe.track_errors(spans, n_groups)
+        if pipe.load is not None:  # the load SLI sees the window's spans and the cut's time
+            pipe.track_load(spans, cut.t_ns, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
