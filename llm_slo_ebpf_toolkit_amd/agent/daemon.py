@@ -275,6 +275,17 @@ class AgentOptions:
     load_factor: float = 1.5             # the ratio that counts as up or down (the smallest clearly not window-to-window noise)
     load_min_requests: int = 20          # fewest recent arrivals for a surge, and a base rate of as many for a drop
     load_min_concurrency: float = 1.0    # least recent concurrency for a slowdown
+    # per service, how much load fits the TTFT SLO: requests and TTFT breaches by the concurrency of the time bin the
+    # request arrived in, the concurrency above which slo_target's error budget is exceeded (the knee) and the recent
+    # concurrency against it (pipeline/satcurve.py, docs/SATURATION_CURVE.md): a saturation field in the decision log
+    # and four series; one GPU; nothing is checkpointed (unknown after a restart). The defaults are reasoned, not tuned
+    saturation_curve: bool = False
+    sat_bin_ms: float = 0.0              # a bin's length (0: window_ms / 4, at least 1 ms)
+    sat_bins: int = 1024                 # bins of the ring per service (a power of two in 64..8192)
+    sat_settle_ms: float = 15000.0       # the newest time left out of every range: a request in flight is invisible
+    sat_recent_ms: float = 15000.0       # the recent range compared with the knee
+    sat_epoch_s: float = 21600.0         # a generation's length: the curve remembers one to two of them
+    sat_min_requests: int = 200          # fewest requests at or above a knee, and fewest in the whole curve
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -829,6 +840,8 @@ class Agent:
                        and g < len(res["err_counts"]) else {}),
                     **({"load": self._load_entry(res, g)} if res.get("load_rows") is not None
                        and g < len(res["load_rows"]) else {}),
+                    **({"saturation": self._saturation_entry(res, g)} if res.get("sat_rows") is not None
+                       and g < len(res["sat_rows"]) else {}),
                     **({"gate": "burn" if burning else ("errors" if erring else "drift")}
                        if emit and (drift_on or err_on) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
@@ -1004,6 +1017,56 @@ class Agent:
         p = self.load_params()
         return summary(res["load_rows"][g], p["bin_us"], p["recent_bins"])
 
+    def saturation_params(self) -> dict:
+        """The saturation curve tracker's parameters from the flags: a bin is --sat-bin-ms or a quarter of the window,
+        1 ms at least; the millisecond flags become bins by ceil; the budget is slo_target's."""
+        p = getattr(self, "_sat_params", None)
+        if p is None:
+            from ..pipeline.satcurve import budget_ppm
+
+            o = self.o
+            ms = float(o.sat_bin_ms)
+            bin_us = max(1000, int(round((ms if ms > 0 else float(o.window_ms) / 4.0) * 1e3)))
+            p = self._sat_params = dict(
+                bin_us=bin_us, settle_bins=max(0, math.ceil(float(o.sat_settle_ms) * 1e3 / bin_us)),
+                recent_bins=max(1, math.ceil(float(o.sat_recent_ms) * 1e3 / bin_us)),
+                epoch_bins=max(1, math.ceil(float(o.sat_epoch_s) * 1e6 / bin_us)),
+                budget_ppm=int(budget_ppm(float(o.slo_target))), min_requests=int(o.sat_min_requests))
+        return dict(p)
+
+    def check_saturation_flags(self) -> None:
+        """Refuse, by flag name, a --sat-* combination the tracker would not take."""
+        from ..pipeline.loadsli import default_ring_records_max
+        from ..pipeline.satcurve import MAX_CURVE_RECORDS, check_config
+
+        o, p = self.o, self.saturation_params()
+        if not (math.isfinite(float(o.sat_settle_ms)) and float(o.sat_settle_ms) >= 0
+                and math.isfinite(float(o.sat_recent_ms)) and float(o.sat_recent_ms) > 0
+                and math.isfinite(float(o.sat_epoch_s)) and float(o.sat_epoch_s) > 0):
+            raise ValueError("--sat-settle-ms must be >= 0, --sat-recent-ms > 0 and --sat-epoch-s > 0")
+        B = int(o.sat_bins)
+        if B >= 64 and not B & (B - 1) and p["settle_bins"] + p["recent_bins"] > B:
+            raise ValueError(f"--sat-settle-ms {o.sat_settle_ms:g} ({p['settle_bins']} bins) + --sat-recent-ms "
+                             f"{o.sat_recent_ms:g} ({p['recent_bins']} bins) do not fit --sat-bins {B} at --sat-bin-ms "
+                             f"{p['bin_us'] / 1000.0:g}")
+        if B >= 64 and not B & (B - 1) and p["epoch_bins"] < B:
+            raise ValueError(f"--sat-epoch-s {o.sat_epoch_s:g} ({p['epoch_bins']} bins) is shorter than the ring: --sat-bins "
+                             f"{B} at --sat-bin-ms {p['bin_us'] / 1000.0:g}")
+        try:
+            check_config(B, p["bin_us"], p["settle_bins"], p["recent_bins"], p["epoch_bins"], p["budget_ppm"],
+                         p["min_requests"], float(self.o.ttft_slo_ms), max(1, int(o.window_spans)),
+                         max(1, int(o.window_groups)), 3, default_ring_records_max(max(B, 1), p["bin_us"]), MAX_CURVE_RECORDS)
+        except ValueError as e:
+            raise ValueError(f"{e} (--sat-bins, --sat-bin-ms, --sat-settle-ms, --sat-recent-ms, --sat-epoch-s, "
+                             "--sat-min-requests)") from None
+
+    def _saturation_entry(self, res: dict, g: int) -> dict:
+        """Group g's saturation curve for the decision log: the state, the knee's and the recent concurrency, their
+        ratio, the curve's totals, the counts at the knee and the curve's levels with requests."""
+        from ..pipeline.satcurve import summary
+
+        return summary(res["sat_rows"][g], res["sat_curve"][g])
+
     def drift_windows(self) -> Tuple[int, int, int]:
         """(R, L, B) of the TTFT drift tracker: the flags, or 10 s / 10 s / 300 s of windows."""
         from ..pipeline.drift import defaults
@@ -1108,6 +1171,8 @@ class Agent:
         if head.get("load_sli") is not None and res.get("load_rows") is not None:
             p = self.load_params()
             self.metrics.observe_load(res, head["load_sli"], names, p["bin_us"], p["recent_bins"])
+        if head.get("saturation") is not None and res.get("sat_rows") is not None:
+            self.metrics.observe_saturation(res, head["saturation"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -1248,6 +1313,11 @@ class Agent:
                              "the device, the load SLI tracker's are read on the host")
         if o.load_sli:  # a combination that does not fit the ring: refused here, naming the flags
             self.check_load_flags()
+        if o.saturation_curve and N > 1:
+            raise ValueError("--saturation-curve runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the saturation curve tracker's are read on the host")
+        if o.saturation_curve:  # a combination that does not fit: refused here, naming the flags
+            self.check_saturation_flags()
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1309,7 +1379,9 @@ class Agent:
                             error_min_requests=int(o.error_min_requests),
                             error_bad_mask=self.error_bad_mask() if o.error_sli else 0xF8,
                             load_sli=int(o.load_bins) if o.load_sli else 0,
-                            load_params=tuple(sorted(self.load_params().items())) if o.load_sli else ())
+                            load_params=tuple(sorted(self.load_params().items())) if o.load_sli else (),
+                            saturation=int(o.sat_bins) if o.saturation_curve else 0,
+                            sat_params=tuple(sorted(self.saturation_params().items())) if o.saturation_curve else ())
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

@@ -208,6 +208,21 @@ class AgentMetrics:
         self.concurrency = r.gauge("llm_slo_agent_concurrency",
                                    "Requests in flight at the service, averaged over the recent and the base range, and "
                                    "the ring's peak.", ("service", "range"))
+        # saturation curve (agent --saturation-curve, pipeline/satcurve.py): how much load fits the TTFT SLO
+        self.saturation_state = r.gauge("llm_slo_agent_saturation_state",
+                                        "Saturation state by service: 0 unknown, 1 no_knee (no concurrency level over the "
+                                        "TTFT SLO's error budget), 2 below the knee, 3 saturated (recent concurrency at or "
+                                        "above the knee).", ("service",))
+        self.saturation_knee = r.gauge("llm_slo_agent_saturation_knee_concurrency",
+                                       "The concurrency above which the service exceeds its TTFT SLO's error budget (the last "
+                                       "valid knee).", ("service",))
+        self.saturation_headroom = r.gauge("llm_slo_agent_saturation_headroom_ratio",
+                                           "Knee concurrency over recent concurrency (the last values with a knee).",
+                                           ("service",))
+        self.saturation_events = r.counter("llm_slo_agent_saturation_events_total",
+                                           "Saturation curve events: out_of_group, invalid (a duration NaN, negative or above "
+                                           "a day), no_time, future, too_old, clipped (started before the ring: not in the "
+                                           "curve), no_ttft (occupies its interval, not in the curve).", ("reason",))
         self.load_events = r.counter("llm_slo_agent_load_events_total",
                                      "Load SLI events: out_of_group (a group beyond the window's), invalid (a duration NaN, "
                                      "negative or above a day), no_time, future (starting or ending ahead of the cut), "
@@ -455,6 +470,22 @@ class AgentMetrics:
                 self.error_firing.set(float((int(firing[g]) >> p) & 1), name, label)
         for reason in EVENT_STATS:
             self.error_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_saturation(self, res: dict, stats: dict, names) -> None:
+        """One window of the saturation curve tracker: ``res`` carries ``sat_rows`` / ``sat_curve`` per group
+        (pipeline/satcurve.py SAT_ROW), ``stats`` by name."""
+        from ..pipeline.satcurve import EVENT_STATS, summary
+
+        for g, row in enumerate(res["sat_rows"]):
+            name = names[g] if g < len(names) else f"group-{g}"
+            s = summary(row, res["sat_curve"][g])
+            self.saturation_state.set(float(int(row["state"])), name)
+            if s["knee_concurrency"] is not None:  # a row without a knee keeps its last values
+                self.saturation_knee.set(float(s["knee_concurrency"]), name)
+                if s["headroom"] is not None:
+                    self.saturation_headroom.set(float(s["headroom"]), name)
+        for reason in EVENT_STATS:
+            self.saturation_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_load(self, res: dict, stats: dict, names, bin_us: int, recent_bins: int) -> None:
         """One window of the load SLI tracker: ``res`` carries ``load_rows`` per group (pipeline/loadsli.py

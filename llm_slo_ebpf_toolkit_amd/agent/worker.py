@@ -105,6 +105,10 @@ class WorkerSpec:
     # its parameters as sorted (name, value) pairs: bin_us, settle_bins, recent_bins, min_base_bins, factor_milli,
     # min_requests, min_conc_milli (agent --load-*; daemon.load_params)
     load_params: Tuple[Tuple[str, int], ...] = ()
+    saturation: int = 0         # bins of the saturation curve's ring per service (agent --saturation-curve, --sat-bins); 0: off
+    # its parameters as sorted (name, value) pairs: bin_us, settle_bins, recent_bins, epoch_bins, budget_ppm,
+    # min_requests (agent --sat-*; daemon.saturation_params)
+    sat_params: Tuple[Tuple[str, int], ...] = ()
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
@@ -131,7 +135,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
                 "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS,
-                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS, "load_rows"):
+                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS, "load_rows", "sat_rows", "sat_curve"):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -211,7 +215,8 @@ class WorkerCore:
                                    error_sli=spec.error_sli, error_target=spec.error_target,
                                    error_pairs=spec.error_pairs, error_min_requests=spec.error_min_requests,
                                    error_bad_mask=spec.error_bad_mask, load_sli=spec.load_sli,
-                                   **{f"load_{name}": int(v) for name, v in spec.load_params})
+                                   **{f"load_{name}": int(v) for name, v in spec.load_params},
+                                   saturation=spec.saturation, **{f"sat_{name}": int(v) for name, v in spec.sat_params})
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -401,6 +406,10 @@ class WorkerCore:
                 from ..pipeline.loadsli import stats_dict as load_stats
 
                 d["load_sli"] = load_stats(pipe.load_results(k, n_groups)["stats"])
+            if pipe.sat is not None:  # the saturation curve tracker's statistics of the window
+                from ..pipeline.satcurve import stats_dict as sat_stats
+
+                d["saturation"] = sat_stats(pipe.saturation_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

@@ -211,6 +211,21 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                                    "rate of as many (reasoned, not tuned)"),
         ("load-min-concurrency", d.load_min_concurrency, "--load-sli: least recent concurrency for a slowdown (reasoned, "
                                                          "not tuned)"),
+        ("saturation-curve", False, "gpu engine: per service, how much load fits the TTFT SLO -- requests and TTFT breaches by "
+                                    "the concurrency of the time bin the request arrived in, kept on the GPU; the "
+                                    "concurrency above which the SLO's error budget is exceeded (the knee) and the recent "
+                                    "concurrency against it -- a saturation field in the decision log, "
+                                    "llm_slo_agent_saturation_state / _knee_concurrency / _headroom_ratio; one GPU only; "
+                                    "nothing is checkpointed (unknown after a restart)"),
+        ("sat-bin-ms", d.sat_bin_ms, "--saturation-curve: a time bin's length (0 = window-ms / 4; at least 1)"),
+        ("sat-bins", d.sat_bins, "--saturation-curve: bins of the ring per service (a power of two in 64..8192)"),
+        ("sat-settle-ms", d.sat_settle_ms, "--saturation-curve: the newest time left out of every range -- a request still "
+                                           "in flight is invisible until it finishes (reasoned, not tuned)"),
+        ("sat-recent-ms", d.sat_recent_ms, "--saturation-curve: the recent range compared with the knee (reasoned, not tuned)"),
+        ("sat-epoch-s", d.sat_epoch_s, "--saturation-curve: a generation's length; the curve remembers one to two of them "
+                                       "(reasoned, not tuned: 6 h spans a working day's peak and trough)"),
+        ("sat-min-requests", d.sat_min_requests, "--saturation-curve: fewest requests at or above a knee, and fewest in the "
+                                                 "whole curve (reasoned, not tuned)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -278,6 +293,9 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         load_sli=bool(a.load_sli), load_bin_ms=float(a.load_bin_ms), load_bins=int(a.load_bins),
         load_settle_ms=float(a.load_settle_ms), load_recent_ms=float(a.load_recent_ms), load_factor=float(a.load_factor),
         load_min_requests=int(a.load_min_requests), load_min_concurrency=float(a.load_min_concurrency),
+        saturation_curve=bool(a.saturation_curve), sat_bin_ms=float(a.sat_bin_ms), sat_bins=int(a.sat_bins),
+        sat_settle_ms=float(a.sat_settle_ms), sat_recent_ms=float(a.sat_recent_ms), sat_epoch_s=float(a.sat_epoch_s),
+        sat_min_requests=int(a.sat_min_requests),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -15,6 +15,7 @@
 #include "errsli.h"
 #include "exemplars.h"
 #include "loadsli.h"
+#include "satcurve.h"
 #include "onset.h"
 #include "openreq.h"
 #include "podrank.h"
@@ -1165,6 +1166,112 @@ class PyLoadSliTracker {
   std::unique_ptr<LoadSliTracker> t_;
 };
 
+// The saturation curve tracker (satcurve.h): one step per timed window cut over the same span ranges
+// the engine gets; results per step index. Rows leave as bytes [G, 64] (pipeline/satcurve.py SAT_ROW),
+// the merged curve as u64 [G, 160, 2].
+class PySaturationTracker {
+ public:
+  PySaturationTracker(int device, int64_t bins, int64_t bin_us, int64_t settle_bins, int64_t recent_bins, int64_t epoch_bins,
+                      int64_t budget_ppm, int64_t min_requests, double slo_ms, int64_t span_cap, int group_cap, int n_buffers,
+                      int64_t ring_records_max, int64_t curve_records_max, bool lds) {
+    if (bins < satcurve::kMinBins || bins > satcurve::kMaxBins)
+      throw std::invalid_argument("saturation curve: bins must be a power of two in [64, 8192]");
+    if (span_cap < 1) throw std::invalid_argument("saturation curve: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("saturation curve: the ring needs more than 2 GiB");
+    auto small = [](int64_t v) { return v < -1 ? -1 : (v > (int64_t(1) << 30) ? (1 << 30) : (int)v); };
+    satcurve::Config c;
+    c.device = device;
+    c.bins = (int)bins;
+    c.bin_us = bin_us;
+    c.settle_bins = small(settle_bins);
+    c.recent_bins = small(recent_bins);
+    c.epoch_bins = epoch_bins;
+    c.budget_ppm = budget_ppm;
+    c.min_requests = min_requests;
+    c.slo_ms = slo_ms;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.n_buffers = n_buffers;
+    c.ring_records_max = ring_records_max;
+    c.curve_records_max = curve_records_max;
+    c.lds = lds;
+    satcurve::validate(c);
+    t_ = std::make_unique<SaturationTracker>(c);
+  }
+  SaturationTracker& t() {
+    if (!t_) throw std::logic_error("saturation curve closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
+    SaturationTracker& st = t();
+    py::gil_scoped_release nogil;
+    return st.step(spans, cut_ns, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  py::dict results(int64_t i, int n_groups) {
+    SaturationTracker& st = t();
+    if (n_groups < 0 || n_groups > st.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = st.results(i);
+    }
+    const satcurve::Layout& l = st.result_layout();
+    py::dict d;
+    d["rows"] = copy_array(reinterpret_cast<const uint8_t*>(r + l.rows), {(py::ssize_t)n_groups, satcurve::kRowBytes});
+    d["curve"] = copy_array(reinterpret_cast<const uint64_t*>(r + l.curve), {(py::ssize_t)n_groups, satcurve::kK, 2});
+    d["stats"] = copy_array(r + l.stats, {satcurve::kStats});
+    return d;
+  }
+  // the step's whole result block, uint32 words
+  py::array_t<uint32_t> block(int64_t i) {
+    SaturationTracker& st = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = st.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)st.result_layout().words});
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (counts, idle_us, sli u64 [group_cap, bins] in slot order, carry, gen u64 [2, group_cap, 160, 2], gen_epoch, age,
+  // q_hi, q_first)
+  py::tuple resident() {
+    SaturationTracker& st = t();
+    satcurve::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = st.resident();
+    }
+    const py::ssize_t G = st.config().group_cap, B = st.config().bins;
+    return py::make_tuple(copy_array(reinterpret_cast<const uint64_t*>(h.counts.data()), {G, B}),
+                          copy_array(reinterpret_cast<const uint64_t*>(h.idle_us.data()), {G, B}),
+                          copy_array(reinterpret_cast<const uint64_t*>(h.sli.data()), {G, B}), copy_array(h.carry.data(), {G}),
+                          copy_array(reinterpret_cast<const uint64_t*>(h.gen.data()), {2, G, satcurve::kK, 2}),
+                          py::make_tuple(h.gen_epoch[0], h.gen_epoch[1]), copy_array(h.age.data(), {G}), h.q_hi, h.q_first);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  std::unique_ptr<SaturationTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -1433,6 +1540,74 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PyLoadSliTracker::resident)
       .def("sync", &PyLoadSliTracker::sync)
       .def("close", &PyLoadSliTracker::close);
+  m.attr("SATCURVE_ROW_BYTES") = satcurve::kRowBytes;
+  m.attr("SATCURVE_STATS") = (int)satcurve::kStats;
+  m.attr("SATCURVE_LEVELS") = satcurve::kK;
+  m.attr("SATCURVE_LDS_SLOTS") = satcurve::kLdsSlots;
+  m.attr("SATCURVE_BINS") = py::make_tuple(satcurve::kMinBins, satcurve::kMaxBins);
+  m.attr("SATCURVE_CURVE_RECORDS_MAX") = satcurve::kMaxCurveRecords;
+  // (u, level) of a busy time over a span of time, and a level's smallest u
+  m.def("satcurve_level", [](int64_t busy_us, int64_t span_us) {
+    if (span_us < 1) throw std::invalid_argument("saturation curve level: empty span");
+    const uint32_t u = satcurve::u_of(busy_us, span_us);
+    return py::make_tuple(u, satcurve::level_of_u(u));
+  });
+  m.def("satcurve_lower", [](uint32_t level) { return satcurve::lower_u(level); });
+  // (level or 0xffffffff, n, b, valid) of a curve u64 [160, 2]
+  m.def("satcurve_knee", [](py::array_t<uint64_t, py::array::c_style | py::array::forcecast> curve, int64_t budget_ppm,
+                            int64_t min_requests) {
+    if (curve.size() != satcurve::kK * 2) throw std::invalid_argument("saturation curve knee: the curve is [160, 2]");
+    const satcurve::Knee k = satcurve::knee_of(curve.data(), budget_ppm, min_requests);
+    return py::make_tuple(k.level, k.n, k.b, k.valid);
+  });
+  m.def("satcurve_state", [](bool recent_known, uint64_t n_total, int64_t min_requests, bool knee_valid, uint32_t recent_level,
+                             uint32_t knee_level) {
+    return satcurve::state_of(recent_known, n_total, min_requests, knee_valid, recent_level, knee_level);
+  });
+  m.def("satcurve_age", [](uint32_t state, uint32_t prev_age) { return satcurve::age_of(state, prev_age); });
+  // (first, count, lo, hi) of the bins an advance evicts and of those it folds
+  m.def("satcurve_fold", [](int64_t prev, int64_t q_hi, int64_t q_first, uint32_t bins) {
+    const satcurve::Fold f = satcurve::fold_of(prev, q_hi, q_first, bins);
+    return py::make_tuple(f.first, f.count, f.lo, f.hi);
+  });
+  m.def("satcurve_layout", [](int group_cap) {
+    const satcurve::Layout l = satcurve::layout(group_cap);
+    py::dict d;
+    d["rows"] = l.rows, d["curve"] = l.curve, d["stats"] = l.stats, d["words"] = l.words;
+    return d;
+  });
+  m.def("satcurve_device_bytes", [](int bins, int64_t span_cap, int group_cap) {
+    return satcurve::device_bytes(bins, (int)span_cap, group_cap);
+  });
+  // the two bounds: the population after a list of (q_hi, spans) steps and one more
+  m.def("satcurve_ring_after", [](uint32_t bins, const std::vector<std::pair<int64_t, int64_t>>& steps, int64_t q_hi, int64_t n) {
+    satcurve::RingPopulation p(bins, INT64_MAX);
+    for (const auto& s : steps) p.take(s.first, (size_t)s.second);
+    return p.after(q_hi, (size_t)n);
+  });
+  m.def("satcurve_curve_after", [](int64_t epoch_bins, const std::vector<std::pair<int64_t, int64_t>>& steps, int64_t q_hi,
+                                   int64_t n) {
+    if (epoch_bins < 1) throw std::invalid_argument("saturation curve: epoch_bins");
+    satcurve::CurvePopulation p(epoch_bins, INT64_MAX);
+    for (const auto& s : steps) p.take(s.first, (size_t)s.second);
+    return p.after(q_hi, (size_t)n);
+  });
+  py::class_<PySaturationTracker>(m, "SaturationTracker")
+      .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, int64_t, int, int, int64_t,
+                    int64_t, bool>(),
+           py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_us") = 500000, py::arg("settle_bins") = 30,
+           py::arg("recent_bins") = 30, py::arg("epoch_bins") = 43200, py::arg("budget_ppm") = 10000,
+           py::arg("min_requests") = 200, py::arg("slo_ms") = 800.0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64,
+           py::arg("n_buffers") = 3, py::arg("ring_records_max") = loadsli::default_ring_records_max(1024, 500000),
+           py::arg("curve_records_max") = satcurve::kMaxCurveRecords, py::arg("lds") = true)
+      .def("step", &PySaturationTracker::step, py::arg("spans"), py::arg("cut_ns"), py::arg("n_groups"))
+      .def("query", &PySaturationTracker::query)
+      .def("results", &PySaturationTracker::results)
+      .def("block", &PySaturationTracker::block)
+      .def("step_ms", &PySaturationTracker::step_ms)
+      .def("resident", &PySaturationTracker::resident)
+      .def("sync", &PySaturationTracker::sync)
+      .def("close", &PySaturationTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

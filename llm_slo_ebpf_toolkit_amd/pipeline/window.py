@@ -108,7 +108,9 @@ class WindowPipeline:
                  error_bad_mask: int = 0xF8, load_sli: int = 0, load_bin_us: Optional[int] = None,
                  load_settle_bins: Optional[int] = None, load_recent_bins: Optional[int] = None,
                  load_min_base_bins: Optional[int] = None, load_factor_milli: int = 1500, load_min_requests: int = 20,
-                 load_min_conc_milli: int = 1000):
+                 load_min_conc_milli: int = 1000, saturation: int = 0, sat_bin_us: Optional[int] = None,
+                 sat_settle_bins: Optional[int] = None, sat_recent_bins: Optional[int] = None,
+                 sat_epoch_bins: Optional[int] = None, sat_budget_ppm: int = 10000, sat_min_requests: int = 200):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -173,7 +175,16 @@ class WindowPipeline:
         as steady, surge, slowdown or drop by ``load_factor_milli``, ``load_min_requests`` and
         ``load_min_conc_milli`` (pipeline/loadsli.py; the device tracker for "gpu", the host oracle for
         "cpu"); ``results()`` then also carries ``load_rows`` / ``load_stats`` (loadsli.RESULT_KEYS). 0: off,
-        nothing is constructed. One GPU only."""
+        nothing is constructed. One GPU only.
+        ``saturation`` > 0: per service, keep the load tracker's ring of that many time bins of ``sat_bin_us``
+        microseconds (default ``window_ms`` / 4) with the requests and the TTFT breaches (above ``ttft_slo_ms``)
+        by the bin they started in, fold the bins that leave it into two generations of ``sat_epoch_bins``
+        bins (default 6 h, the ring's length at least) by the bin's concurrency level, and report every window
+        the merged curve, the concurrency above which ``sat_budget_ppm`` is exceeded (the knee, over at least
+        ``sat_min_requests`` requests) and the concurrency of the ``sat_recent_bins`` bins before the newest
+        ``sat_settle_bins`` (defaults: 15 s each, in bins) against it (pipeline/satcurve.py; the device tracker
+        for "gpu", the host oracle for "cpu"); ``results()`` then also carries ``sat_rows`` / ``sat_curve`` /
+        ``sat_stats`` (satcurve.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -387,9 +398,33 @@ class WindowPipeline:
                 from .loadsli import LoadSliOracle
 
                 self.load = LoadSliOracle(**lkw)
+        self.sat = None
+        self.sat_skipped = 0  # cuts without a time (replay helpers): no tracker step
+        self._sat: Dict[int, Tuple[int, Optional[int]]] = {}  # buffer -> (window, tracker step)
+        if saturation:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the saturation curve runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            bin_us = max(1000, int(round(window_ms * 1e3 / 4))) if sat_bin_us is None else int(sat_bin_us)
+            per_15s = -(-15_000_000 // max(bin_us, 1))
+            skw = dict(bins=int(saturation), bin_us=bin_us,
+                       settle_bins=per_15s if sat_settle_bins is None else int(sat_settle_bins),
+                       recent_bins=per_15s if sat_recent_bins is None else int(sat_recent_bins),
+                       epoch_bins=max(int(saturation), -(-21_600_000_000 // max(bin_us, 1))) if sat_epoch_bins is None
+                       else int(sat_epoch_bins),
+                       budget_ppm=int(sat_budget_ppm), min_requests=int(sat_min_requests), slo_ms=float(ttft_slo_ms),
+                       span_cap=span_cap, group_cap=group_cap, n_buffers=self.nb, device=device)
+            if engine == "gpu":
+                from ..ops.satcurve import SaturationTracker
+
+                self.sat = SaturationTracker(**skw)
+            else:
+                from .satcurve import SaturationOracle
+
+                self.sat = SaturationOracle(**skw)
         # the side trackers are fixed from here on: copy_ahead asks once per window and half
         self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
-                                                        self.decode, self.drift, self.errors, self.load))
+                                                        self.decode, self.drift, self.errors, self.load, self.sat))
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -547,6 +582,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(load_keys(self.load_results(k, n_groups)))
+        if self.sat is not None:
+            from .satcurve import result_keys as sat_keys
+
+            res = dict(res)
+            res.update(sat_keys(self.saturation_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -726,9 +766,34 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- saturation curve (pipeline/satcurve.py) --------------------------------------------
+    def track_saturation(self, spans, cut_ns: int, n_groups: int) -> None:
+        """The saturation tracker's step for the window about to be submitted: the same span ranges and
+        the cut's time. A cut without a time is skipped and counted."""
+        if self.sat is None:
+            return
+        step = None
+        if int(cut_ns) > 0:
+            step = self.sat.step(list(spans), int(cut_ns), int(n_groups))
+        else:
+            self.sat_skipped += 1
+        self._sat[self.k % self.nb] = (self.k, step)
+
+    def saturation_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The saturation tracker's results of window k (pipeline/satcurve.py RESULT_FIELDS; empty_result
+        for a window it skipped)."""
+        held = self._sat.get(k % self.nb)
+        if held is not None and held[0] == k and held[1] is not None:
+            return self.sat.results(held[1], n_groups)
+        from .satcurve import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.sat is not None:
+            self.sat.close()
         if self.load is not None:
             self.load.close()
         if self.errors is not None:
@@ -799,6 +864,8 @@ class WindowPipeline:
             self.errors.sync()
         if self.load is not None:
             self.load.sync()
+        if self.sat is not None:
+            self.sat.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -1126,6 +1193,8 @@ class RingWindowSource:
             pipe.track_errors(spans, n_groups)
         if pipe.load is not None:  # the load SLI sees the window's spans and the cut's time
             pipe.track_load(spans, cut.t_ns, n_groups)
+        if pipe.sat is not None:  # the saturation curve sees the window's spans and the cut's time
+            pipe.track_saturation(spans, cut.t_ns, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
