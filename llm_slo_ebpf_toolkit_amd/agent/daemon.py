@@ -286,6 +286,16 @@ class AgentOptions:
     sat_recent_ms: float = 15000.0       # the recent range compared with the knee
     sat_epoch_s: float = 21600.0         # a generation's length: the curve remembers one to two of them
     sat_min_requests: int = 200          # fewest requests at or above a knee, and fewest in the whole curve
+    # per service, TTFT split into the retrieval time the trace's first record carries and the model time left: both
+    # distributions, the requests by TTFT-breach phase and a verdict over a rolling horizon, on the GPU
+    # (pipeline/retrsli.py, docs/RETRIEVAL_SLI.md): a retrieval field in the decision log and six series; one GPU;
+    # nothing is checkpointed (unknown after a restart). The defaults are reasoned, not tuned
+    retrieval_sli: bool = False
+    retrieval_budget_ms: float = 0.0     # retrieval's own budget (0: a quarter of ttft_slo_ms, which leaves prefill three)
+    retrieval_horizon_windows: int = 0   # windows of the rolling horizon (0: the TTFT sketch's)
+    retrieval_min_requests: int = 200    # fewest requests with a breakdown for a verdict (the saturation curve's reason)
+    retrieval_min_coverage: float = 0.5  # fewest requests with a breakdown, as a share of the SLI records
+    retrieval_dominance: float = 0.667   # share of the breaches one phase needs: it explains twice what the rest does
     explicit_flags: Tuple[str, ...] = ()  # flags given on the command line (they win over the config's gpu: block)
 
 
@@ -842,6 +852,8 @@ class Agent:
                        and g < len(res["load_rows"]) else {}),
                     **({"saturation": self._saturation_entry(res, g)} if res.get("sat_rows") is not None
                        and g < len(res["sat_rows"]) else {}),
+                    **({"retrieval": self._retrieval_entry(res, g)} if res.get("retr_cells") is not None
+                       and g < len(res["retr_cells"]) else {}),
                     **({"gate": "burn" if burning else ("errors" if erring else "drift")}
                        if emit and (drift_on or err_on) else {}),
                     "why": "emitted" if emit else ("low_confidence" if not confident else
@@ -1067,6 +1079,51 @@ class Agent:
 
         return summary(res["sat_rows"][g], res["sat_curve"][g])
 
+    def retrieval_horizon(self) -> int:
+        """Windows of the TTFT phase split's rolling horizon: the flag, or the TTFT sketch's."""
+        w = int(self.o.retrieval_horizon_windows)
+        return w if w > 0 else self.ttft_horizon()
+
+    def retrieval_budget_ms(self) -> float:
+        """Retrieval's own budget: the flag, or a quarter of the TTFT SLO."""
+        ms = float(self.o.retrieval_budget_ms)
+        return ms if ms != 0 else float(self.o.ttft_slo_ms) / 4.0
+
+    def retrieval_params(self) -> dict:
+        """The TTFT phase split's thresholds from the flags: the shares become millionths (round half up); the error
+        budget is slo_target's."""
+        from ..pipeline.retrsli import budget_ppm
+
+        o = self.o
+        for flag, v in (("--retrieval-min-coverage", o.retrieval_min_coverage), ("--retrieval-dominance", o.retrieval_dominance)):
+            if not (math.isfinite(float(v)) and 0.0 <= float(v) <= 1.0):
+                raise ValueError(f"{flag} must be a share in [0, 1]")
+        return dict(budget_ppm=int(budget_ppm(float(o.slo_target))),
+                    coverage_ppm=int(float(o.retrieval_min_coverage) * 1e6 + 0.5),
+                    dominance_ppm=int(float(o.retrieval_dominance) * 1e6 + 0.5), min_requests=int(o.retrieval_min_requests))
+
+    def check_retrieval_flags(self) -> None:
+        """Refuse, by flag name, a --retrieval-* combination the tracker would not take."""
+        from ..pipeline.retrsli import check_config
+
+        p = self.retrieval_params()
+        try:
+            check_config(max(1, int(self.o.window_spans)), max(1, int(self.o.window_groups)), self.retrieval_horizon(), 3,
+                         float(self.o.ttft_slo_ms), self.retrieval_budget_ms(), **p)
+        except ValueError as e:
+            raise ValueError(f"{e} (--retrieval-budget-ms, --retrieval-horizon-windows, --retrieval-min-requests, "
+                             "--retrieval-min-coverage, --retrieval-dominance, --slo-target)") from None
+
+    @staticmethod
+    def _retrieval_entry(res: dict, g: int) -> dict:
+        """Group g's TTFT phase split for the decision log: the horizon's verdict and the windows it has held, the
+        window's requests with a breakdown, their coverage, retrieval's share of TTFT, the requests by breach phase
+        and the retrieval and model time quantiles and means, and the same over the horizon; ``None`` where a
+        denominator is none."""
+        from ..pipeline.retrsli import entry
+
+        return entry(res, g)
+
     def drift_windows(self) -> Tuple[int, int, int]:
         """(R, L, B) of the TTFT drift tracker: the flags, or 10 s / 10 s / 300 s of windows."""
         from ..pipeline.drift import defaults
@@ -1173,6 +1230,8 @@ class Agent:
             self.metrics.observe_load(res, head["load_sli"], names, p["bin_us"], p["recent_bins"])
         if head.get("saturation") is not None and res.get("sat_rows") is not None:
             self.metrics.observe_saturation(res, head["saturation"], names)
+        if head.get("retrieval_sli") is not None and res.get("retr_cells") is not None:
+            self.metrics.observe_retrieval(res, head["retrieval_sli"], names)
         attrs = self._attributions(G, names, res, t_ns, model)
         for attr in attrs:
             self.metrics.observe_attribution(attr.predicted_fault_domain)
@@ -1318,6 +1377,11 @@ class Agent:
                              "the device, the saturation curve tracker's are read on the host")
         if o.saturation_curve:  # a combination that does not fit: refused here, naming the flags
             self.check_saturation_flags()
+        if o.retrieval_sli and N > 1:
+            raise ValueError("--retrieval-sli runs on one GPU (--gpus 1): the workers' results are gathered on "
+                             "the device, the retrieval SLI tracker's are read on the host")
+        if o.retrieval_sli:  # a value the tracker would not take: refused here, naming the flags
+            self.check_retrieval_flags()
         # a replay producer forks here, before any GPU work
         maps, sets, pods = self._open_source(N if split else 1)
         ring, user, spans = sets[0]
@@ -1381,7 +1445,10 @@ class Agent:
                             load_sli=int(o.load_bins) if o.load_sli else 0,
                             load_params=tuple(sorted(self.load_params().items())) if o.load_sli else (),
                             saturation=int(o.sat_bins) if o.saturation_curve else 0,
-                            sat_params=tuple(sorted(self.saturation_params().items())) if o.saturation_curve else ())
+                            sat_params=tuple(sorted(self.saturation_params().items())) if o.saturation_curve else (),
+                            retrieval_sli=self.retrieval_horizon() if o.retrieval_sli else 0,
+                            retr_budget_ms=self.retrieval_budget_ms() if o.retrieval_sli else 200.0,
+                            retr_params=tuple(sorted(self.retrieval_params().items())) if o.retrieval_sli else ())
                  for r in range(N)]
         state = self._state_path()
         if state and os.path.exists(state):

@@ -223,6 +223,29 @@ class AgentMetrics:
                                            "Saturation curve events: out_of_group, invalid (a duration NaN, negative or above "
                                            "a day), no_time, future, too_old, clipped (started before the ring: not in the "
                                            "curve), no_ttft (occupies its interval, not in the curve).", ("reason",))
+        # TTFT phase split (agent --retrieval-sli, pipeline/retrsli.py): retrieval against model time
+        self.retrieval_quantile = r.gauge("llm_slo_agent_retrieval_ms",
+                                          "Retrieval time quantile (ms) by service over the last "
+                                          "--retrieval-horizon-windows windows, of the requests that report a breakdown, "
+                                          "from the histogram on the GPU (within 1/32 of the nearest-rank value).",
+                                          ("service", "quantile"))
+        self.model_ttft_quantile = r.gauge("llm_slo_agent_model_ttft_ms",
+                                           "Model time quantile (ms), TTFT minus retrieval, by service over the last "
+                                           "--retrieval-horizon-windows windows.", ("service", "quantile"))
+        self.retrieval_share = r.gauge("llm_slo_agent_retrieval_share",
+                                       "Retrieval time over TTFT, summed over the service's requests with a breakdown in "
+                                       "the last --retrieval-horizon-windows windows.", ("service",))
+        self.ttft_phase_state = r.gauge("llm_slo_agent_ttft_phase_state",
+                                        "Which phase the service's TTFT breaches come from over the horizon: 0 unknown, 1 ok "
+                                        "(within the error budget), 2 retrieval_bound, 3 model_bound, 4 mixed.", ("service",))
+        self.ttft_breach_phase = r.counter("llm_slo_agent_ttft_breach_phase_total",
+                                           "Requests with a retrieval breakdown by service and TTFT-breach phase: ok, "
+                                           "ok_slow_retrieval, model, model_slow_retrieval, retrieval, combined.",
+                                           ("service", "phase"))
+        self.retrieval_events = r.counter("llm_slo_agent_retrieval_events_total",
+                                          "Retrieval SLI events: out_of_group, invalid (ttft NaN or negative), no_breakdown "
+                                          "(no retrieval time), extra (a breakdown on a record whose SLI was counted "
+                                          "already), exceeds_ttft (retrieval above the TTFT).", ("reason",))
         self.load_events = r.counter("llm_slo_agent_load_events_total",
                                      "Load SLI events: out_of_group (a group beyond the window's), invalid (a duration NaN, "
                                      "negative or above a day), no_time, future (starting or ending ahead of the cut), "
@@ -486,6 +509,29 @@ class AgentMetrics:
                     self.saturation_headroom.set(float(s["headroom"]), name)
         for reason in EVENT_STATS:
             self.saturation_events.inc(float(stats.get(reason, 0)), reason)
+
+    def observe_retrieval(self, res: dict, stats: dict, names) -> None:
+        """One window of the retrieval SLI tracker: ``res`` carries the retr_* arrays per group
+        (pipeline/retrsli.py RESULT_KEYS), ``stats`` by name."""
+        from ..pipeline.retrsli import CELLS, EVENT_STATS, QUANTILE_NAMES
+
+        roll = np.asarray(res["retr_cells_roll"], dtype=np.int64)
+        for g, cells in enumerate(np.asarray(res["retr_cells"], dtype=np.int64).tolist()):
+            name = names[g] if g < len(names) else f"group-{g}"
+            for phase, n in zip(CELLS, cells):
+                if n:
+                    self.ttft_breach_phase.inc(float(n), name, phase)
+            self.ttft_phase_state.set(float(int(res["retr_state"][g])), name)
+            if int(roll[g].sum()):  # an empty horizon keeps its last values: NaN would break rate() and min()
+                for q, v, m in zip(QUANTILE_NAMES, np.asarray(res["retr_q_roll"][g], dtype=np.float64).tolist(),
+                                   np.asarray(res["retr_model_q_roll"][g], dtype=np.float64).tolist()):
+                    self.retrieval_quantile.set(v, name, q)
+                    self.model_ttft_quantile.set(m, name, q)
+                total = float(res["retr_ttft_sum_ms_roll"][g])
+                if total > 0:
+                    self.retrieval_share.set(float(res["retr_sum_ms_roll"][g]) / total, name)
+        for reason in EVENT_STATS:
+            self.retrieval_events.inc(float(stats.get(reason, 0)), reason)
 
     def observe_load(self, res: dict, stats: dict, names, bin_us: int, recent_bins: int) -> None:
         """One window of the load SLI tracker: ``res`` carries ``load_rows`` per group (pipeline/loadsli.py

@@ -109,6 +109,11 @@ class WorkerSpec:
     # its parameters as sorted (name, value) pairs: bin_us, settle_bins, recent_bins, epoch_bins, budget_ppm,
     # min_requests (agent --sat-*; daemon.saturation_params)
     sat_params: Tuple[Tuple[str, int], ...] = ()
+    retrieval_sli: int = 0      # windows of the TTFT phase split's rolling horizon (agent --retrieval-sli); 0: off
+    retr_budget_ms: float = 200.0  # retrieval's own budget (agent --retrieval-budget-ms; a quarter of the TTFT SLO)
+    # its thresholds as sorted (name, value) pairs: budget_ppm, coverage_ppm, dominance_ppm, min_requests
+    # (agent --retrieval-*; daemon.retrieval_params)
+    retr_params: Tuple[Tuple[str, int], ...] = ()
 
 
 # the pod breakdown's per-group results (pipeline/podrank.py RESULT_KEYS)
@@ -120,6 +125,10 @@ DRIFT_RESULT_KEYS = ("drift_state", "drift_hold", "drift_n_win", "drift_n_recent
                      "drift_slow_num", "drift_fast_num", "drift_q_recent", "drift_q_base")
 # the error SLI's (pipeline/errsli.py RESULT_KEYS)
 ERROR_RESULT_KEYS = ("err_counts", "err_counts_roll", "err_pair_sums", "err_firing", "err_age")
+# the TTFT phase split's (pipeline/retrsli.py RESULT_KEYS)
+RETR_RESULT_KEYS = ("retr_cells", "retr_cells_roll", "retr_sum_ms", "retr_ttft_sum_ms", "retr_sum_ms_roll",
+                    "retr_ttft_sum_ms_roll", "retr_sli", "retr_sli_roll", "retr_q", "retr_q_roll", "retr_model_q",
+                    "retr_model_q_roll", "retr_state", "retr_age")
 
 
 def groups_of(rank: int, world: int, n_groups: int) -> int:
@@ -135,7 +144,7 @@ def merge_results(parts: List[dict], n_groups: int) -> dict:
     for key in ("post", "conf", "feat", "pred", "evbits", "sli", "app", "late", "sli_raw", "late_raw", "deadline",
                 "deadline_dup", "ttft_n", "ttft_sum_ms", "ttft_le", "ttft_q", "ttft_q_roll", "ttft_n_roll", "ex_n",
                 "ex_k_win", "ex_win", "ex_k_recent", "ex_recent", *POD_RESULT_KEYS, "onset_rows", *DECODE_RESULT_KEYS,
-                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS, "load_rows", "sat_rows", "sat_curve"):
+                *DRIFT_RESULT_KEYS, *ERROR_RESULT_KEYS, "load_rows", "sat_rows", "sat_curve", *RETR_RESULT_KEYS):
         if key not in parts[0]:
             continue
         ref = np.asarray(parts[0][key])
@@ -216,7 +225,9 @@ class WorkerCore:
                                    error_pairs=spec.error_pairs, error_min_requests=spec.error_min_requests,
                                    error_bad_mask=spec.error_bad_mask, load_sli=spec.load_sli,
                                    **{f"load_{name}": int(v) for name, v in spec.load_params},
-                                   saturation=spec.saturation, **{f"sat_{name}": int(v) for name, v in spec.sat_params})
+                                   saturation=spec.saturation, **{f"sat_{name}": int(v) for name, v in spec.sat_params},
+                                   retrieval_sli=spec.retrieval_sli, retr_budget_ms=spec.retr_budget_ms,
+                                   **{f"retr_{name}": int(v) for name, v in spec.retr_params})
         # the controller publishes the epochs: this source never writes mislo_cfg. Split rings are
         # this worker's alone: it frees their space itself
         self.src = RingWindowSource(self.pipe, ring, user, spans, cfg_set=lambda i, v: None,
@@ -410,6 +421,10 @@ class WorkerCore:
                 from ..pipeline.satcurve import stats_dict as sat_stats
 
                 d["saturation"] = sat_stats(pipe.saturation_results(k, n_groups)["stats"])
+            if pipe.retr is not None:  # the TTFT phase split tracker's statistics of the window
+                from ..pipeline.retrsli import stats_dict as retr_stats
+
+                d["retrieval_sli"] = retr_stats(pipe.retrieval_results(k, n_groups)["stats"])
         return d
 
     def stop(self) -> dict:

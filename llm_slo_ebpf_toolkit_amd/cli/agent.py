@@ -226,6 +226,24 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
                                        "(reasoned, not tuned: 6 h spans a working day's peak and trough)"),
         ("sat-min-requests", d.sat_min_requests, "--saturation-curve: fewest requests at or above a knee, and fewest in the "
                                                  "whole curve (reasoned, not tuned)"),
+        ("retrieval-sli", False, "gpu engine: per service, TTFT split into the retrieval time the application reports "
+                                 "(llm.slo.retrieval.*_ms, on the trace's first record) and the model time left -- both "
+                                 "distributions, the requests by TTFT-breach phase and a verdict (retrieval_bound, model_bound, "
+                                 "mixed) over a rolling horizon, on the GPU -- a retrieval field in the decision log, "
+                                 "llm_slo_agent_retrieval_ms / _model_ttft_ms / _retrieval_share / _ttft_phase_state; one GPU "
+                                 "only; nothing is checkpointed (unknown after a restart)"),
+        ("retrieval-budget-ms", d.retrieval_budget_ms, "--retrieval-sli: retrieval's own budget, ms (0 = a quarter of "
+                                                       "ttft-slo-ms; reasoned, not tuned: it leaves prefill three quarters)"),
+        ("retrieval-horizon-windows", d.retrieval_horizon_windows, "--retrieval-sli: windows of the rolling horizon (0 = "
+                                                                   "--ttft-horizon-windows)"),
+        ("retrieval-min-requests", d.retrieval_min_requests, "--retrieval-sli: fewest requests with a breakdown over the "
+                                                             "horizon for a verdict (reasoned, not tuned: the saturation "
+                                                             "curve's reason)"),
+        ("retrieval-min-coverage", d.retrieval_min_coverage, "--retrieval-sli: fewest requests with a breakdown, as a share of "
+                                                             "the SLI records, for a verdict (reasoned, not tuned)"),
+        ("retrieval-dominance", d.retrieval_dominance, "--retrieval-sli: share of the breaches one phase needs for a *_bound "
+                                                       "verdict, above 0.5 (reasoned, not tuned: two thirds means one phase "
+                                                       "explains twice what the rest does)"),
         ("halo-ms", d.halo_ms, "gpu engine: records this close to a window's end also join the next window (0 = off)"),
         ("state-dir", d.state_dir, "gpu engine: checkpoint directory for the learned state (resumed on start)"),
         ("checkpoint-every", d.checkpoint_every, "gpu engine: windows between checkpoints"),
@@ -296,6 +314,9 @@ def parse(argv: List[str]) -> (AgentOptions, bool):
         saturation_curve=bool(a.saturation_curve), sat_bin_ms=float(a.sat_bin_ms), sat_bins=int(a.sat_bins),
         sat_settle_ms=float(a.sat_settle_ms), sat_recent_ms=float(a.sat_recent_ms), sat_epoch_s=float(a.sat_epoch_s),
         sat_min_requests=int(a.sat_min_requests),
+        retrieval_sli=bool(a.retrieval_sli), retrieval_budget_ms=float(a.retrieval_budget_ms),
+        retrieval_horizon_windows=int(a.retrieval_horizon_windows), retrieval_min_requests=int(a.retrieval_min_requests),
+        retrieval_min_coverage=float(a.retrieval_min_coverage), retrieval_dominance=float(a.retrieval_dominance),
         explicit_flags=tuple(sorted({x.lstrip("-").split("=", 1)[0] for x in (argv if argv is not None else sys.argv[1:]) if x.startswith("-")})))
     if int(a.gpu_hw_queues) > 0:  # before anything initialises the HIP runtime
         given = any(x.lstrip("-").split("=", 1)[0] == "gpu-hw-queues" for x in argv or [])

@@ -117,7 +117,7 @@ def build_hip_ext(force: bool = False, jobs: int = 4) -> str:
 
 AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip", "openreq.hip", "slisketch.hip", "exemplars.hip",
                  "podrank.hip", "onset.hip", "decodesli.hip", "drift.hip", "errsli.hip", "loadsli.hip",
-                 "satcurve.hip"]
+                 "satcurve.hip", "retrsli.hip"]
 
 
 def build_agent_ext(force: bool = False, jobs: int = 4) -> str:
@@ -133,7 +133,7 @@ def build_agent_ext(force: bool = False, jobs: int = 4) -> str:
         obj = os.path.join(BUILD, src + ".o")
         objs.append(obj)
         path = os.path.join(CSRC, src)
-        # kernels of the agent alone (open-request tracker, TTFT sketch, request exemplars, pod breakdown, breach onset, decode SLI, TTFT drift, error SLI, load SLI, saturation curve) are compiled here
+        # kernels of the agent alone (open-request tracker, TTFT sketch, request exemplars, pod breakdown, breach onset, decode SLI, TTFT drift, error SLI, load SLI, saturation curve, TTFT phase split) are compiled here
         if src not in HIP_SOURCES and (force or _newer(obj, [path] + hdrs)):
             jobs_list.append([HIPCC, *common, "-c", path, "-o", obj])
     eng = os.path.join(CSRC, "engine.hip")

@@ -19,6 +19,7 @@
 #include "onset.h"
 #include "openreq.h"
 #include "podrank.h"
+#include "retrsli.h"
 #include "slisketch.h"
 
 namespace py = pybind11;
@@ -1272,6 +1273,127 @@ class PySaturationTracker {
   std::unique_ptr<SaturationTracker> t_;
 };
 
+// The TTFT phase split tracker (retrsli.h): one step per window over the same span ranges the engine
+// gets; results per step index (pipeline/retrsli.py RESULT_FIELDS).
+class PyRetrievalSliTracker {
+ public:
+  PyRetrievalSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double slo_ms,
+                        double retrieval_budget_ms, int64_t budget_ppm, int64_t coverage_ppm, int64_t dominance_ppm,
+                        int64_t min_requests, bool lds) {
+    if (span_cap < 1) throw std::invalid_argument("retrieval sli: span_cap must be >= 1");
+    if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("retrieval sli: the horizon needs more than 2 GiB");
+    retrsli::Config c;
+    c.device = device;
+    c.span_cap = (int)span_cap;
+    c.group_cap = group_cap;
+    c.windows = windows;
+    c.n_buffers = n_buffers;
+    c.slo_ms = slo_ms;
+    c.retrieval_budget_ms = retrieval_budget_ms;
+    c.budget_ppm = budget_ppm;
+    c.coverage_ppm = coverage_ppm;
+    c.dominance_ppm = dominance_ppm;
+    c.min_requests = min_requests;
+    c.lds = lds;
+    retrsli::validate(c);
+    t_ = std::make_unique<RetrievalSliTracker>(c);
+  }
+  RetrievalSliTracker& t() {
+    if (!t_) throw std::logic_error("retrieval sli closed");
+    return *t_;
+  }
+  int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
+    RetrievalSliTracker& rs = t();
+    py::gil_scoped_release nogil;
+    return rs.step(spans, n_groups);
+  }
+  bool query(int64_t i) { return t().query(i); }
+  // the whole result block of step i as it left the device (uint32 words)
+  py::array_t<uint32_t> block(int64_t i) {
+    RetrievalSliTracker& rs = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = rs.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)rs.result_layout().words});
+  }
+  py::dict results(int64_t i, int n_groups) {
+    RetrievalSliTracker& rs = t();
+    if (n_groups < 0 || n_groups > rs.config().group_cap) throw std::invalid_argument("n_groups");
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = rs.results(i);
+    }
+    const retrsli::Layout& l = rs.result_layout();
+    const py::ssize_t G = n_groups;
+    const auto sums = [&](size_t at) { return copy_array(reinterpret_cast<const uint64_t*>(r + at), {G}); };
+    py::dict d;
+    d["cells"] = cut_cells(r + l.cells, G);
+    d["cells_roll"] = cut_cells(r + l.cells_roll, G);
+    d["sum_r"] = sums(l.sum_r);
+    d["sum_t"] = sums(l.sum_t);
+    d["sum_r_roll"] = sums(l.sum_r_roll);
+    d["sum_t_roll"] = sums(l.sum_t_roll);
+    d["sli"] = copy_array(r + l.sli, {G});
+    d["sli_roll"] = copy_array(r + l.sli_roll, {G});
+    d["q_r_win"] = copy_array(r + l.q_r_win, {G, retrsli::kQuantiles});
+    d["q_r_roll"] = copy_array(r + l.q_r_roll, {G, retrsli::kQuantiles});
+    d["q_m_win"] = copy_array(r + l.q_m_win, {G, retrsli::kQuantiles});
+    d["q_m_roll"] = copy_array(r + l.q_m_roll, {G, retrsli::kQuantiles});
+    d["state"] = copy_array(r + l.state, {G});
+    d["age"] = copy_array(r + l.age, {G});
+    d["stats"] = copy_array(r + l.stats, {retrsli::kStats});
+    return d;
+  }
+  py::tuple step_ms(int64_t i) {
+    std::vector<float> ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::make_tuple(ms[0], ms[1], ms[2]);
+  }
+  // (rolling retrieval rows u32 [group_cap, K], rolling model rows, rolling cells u32 [group_cap, 6], rolling sli u32
+  // [group_cap], rolling sums u64 [group_cap, 2], state, age, ring position)
+  py::tuple resident() {
+    RetrievalSliTracker& rs = t();
+    retrsli::Resident h;
+    {
+      py::gil_scoped_release nogil;
+      h = rs.resident();
+    }
+    const py::ssize_t G = rs.config().group_cap;
+    py::array_t<uint32_t> sli({G});
+    for (py::ssize_t g = 0; g < G; ++g) sli.mutable_data()[g] = h.cells[(size_t)g * retrsli::kCellStride + retrsli::kSliWord];
+    return py::make_tuple(copy_array(h.rows_r.data(), {G, retrsli::kK}), copy_array(h.rows_m.data(), {G, retrsli::kK}),
+                          cut_cells(h.cells.data(), G), sli, copy_array(reinterpret_cast<const uint64_t*>(h.sums.data()), {G, 2}),
+                          copy_array(h.state.data(), {G}), copy_array(h.age.data(), {G}), h.pos);
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ private:
+  // [G][kCellStride] words -> the six cells of each row
+  static py::array_t<uint32_t> cut_cells(const uint32_t* p, py::ssize_t G) {
+    py::array_t<uint32_t> a({G, (py::ssize_t)retrsli::kCells});
+    for (py::ssize_t g = 0; g < G; ++g)
+      std::memcpy(a.mutable_data() + g * retrsli::kCells, p + g * retrsli::kCellStride, retrsli::kCells * sizeof(uint32_t));
+    return a;
+  }
+
+  std::unique_ptr<RetrievalSliTracker> t_;
+};
+
 py::bytes unique_id() {
   ncclUniqueId u;
   const ncclResult_t r = ncclGetUniqueId(&u);
@@ -1608,6 +1730,48 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("resident", &PySaturationTracker::resident)
       .def("sync", &PySaturationTracker::sync)
       .def("close", &PySaturationTracker::close);
+  m.attr("RETRSLI_K") = retrsli::kK;
+  m.attr("RETRSLI_STATS") = (int)retrsli::kStats;
+  m.attr("RETRSLI_CELLS") = retrsli::kCells;
+  m.attr("RETRSLI_LDS_SLOTS") = retrsli::kLdsSlots;
+  m.attr("RETRSLI_UNIT_MAX") = retrsli::kUnitMax;
+  m.def("retrsli_units_of_ms", [](float ms) { return retrsli::units_of_ms(ms); });
+  m.def("retrsli_budget_units", [](double ms) { return retrsli::budget_units(ms); });
+  m.def("retrsli_cell_of", [](bool tb, uint32_t r, uint32_t m_u, uint32_t slo_u, uint32_t budget_u) {
+    return retrsli::cell_of(tb, r, m_u, slo_u, budget_u);
+  });
+  m.def("retrsli_state_of", [](const std::vector<uint32_t>& cells, uint32_t sli, uint32_t min_requests, uint32_t coverage_ppm,
+                               uint32_t budget_ppm, uint32_t dominance_ppm) {
+    if (cells.size() != (size_t)retrsli::kCells) throw std::invalid_argument("retrieval sli: six cells");
+    retrsli::Thresholds th;
+    th.min_requests = min_requests;
+    th.coverage_ppm = coverage_ppm;
+    th.budget_ppm = budget_ppm;
+    th.dominance_ppm = dominance_ppm;
+    return retrsli::state_of(cells.data(), sli, th);
+  });
+  m.def("retrsli_age_of", [](uint32_t state, uint32_t prev_state, uint32_t prev_age) {
+    return retrsli::age_of(state, prev_state, prev_age);
+  });
+  m.def("retrsli_layout", [](int group_cap) {
+    const retrsli::Layout l = retrsli::layout(group_cap);
+    return std::vector<size_t>{l.cells, l.cells_roll, l.sum_r, l.sum_t, l.sum_r_roll, l.sum_t_roll, l.sli, l.sli_roll, l.q_r_win,
+                               l.q_r_roll, l.q_m_win, l.q_m_roll, l.state, l.age, l.stats, l.words};
+  });
+  py::class_<PyRetrievalSliTracker>(m, "RetrievalSliTracker")
+      .def(py::init<int, int64_t, int, int, int, double, double, int64_t, int64_t, int64_t, int64_t, bool>(),
+           py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 150,
+           py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("retrieval_budget_ms") = 200.0,
+           py::arg("budget_ppm") = 10000, py::arg("coverage_ppm") = 500000, py::arg("dominance_ppm") = 667000,
+           py::arg("min_requests") = 200, py::arg("lds") = true)
+      .def("step", &PyRetrievalSliTracker::step, py::arg("spans"), py::arg("n_groups"))
+      .def("query", &PyRetrievalSliTracker::query)
+      .def("results", &PyRetrievalSliTracker::results)
+      .def("block", &PyRetrievalSliTracker::block)
+      .def("step_ms", &PyRetrievalSliTracker::step_ms)
+      .def("resident", &PyRetrievalSliTracker::resident)
+      .def("sync", &PyRetrievalSliTracker::sync)
+      .def("close", &PyRetrievalSliTracker::close);
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

@@ -110,7 +110,9 @@ class WindowPipeline:
                  load_min_base_bins: Optional[int] = None, load_factor_milli: int = 1500, load_min_requests: int = 20,
                  load_min_conc_milli: int = 1000, saturation: int = 0, sat_bin_us: Optional[int] = None,
                  sat_settle_bins: Optional[int] = None, sat_recent_bins: Optional[int] = None,
-                 sat_epoch_bins: Optional[int] = None, sat_budget_ppm: int = 10000, sat_min_requests: int = 200):
+                 sat_epoch_bins: Optional[int] = None, sat_budget_ppm: int = 10000, sat_min_requests: int = 200,
+                 retrieval_sli: int = 0, retr_budget_ms: Optional[float] = None, retr_min_requests: int = 200,
+                 retr_coverage_ppm: int = 500000, retr_dominance_ppm: int = 667000, retr_budget_ppm: int = 10000):
         """``engine``: "gpu" = the native WindowEngine on HIP device ``device`` (``comm`` = its RCCL
         communicator); "cpu" = pipeline.cpu.CpuRingEngine, the same contract on the host, with
         ``group`` (a torch.distributed gloo group) as its communicator. ``shard`` = (rank, world):
@@ -184,7 +186,14 @@ class WindowPipeline:
         ``sat_min_requests`` requests) and the concurrency of the ``sat_recent_bins`` bins before the newest
         ``sat_settle_bins`` (defaults: 15 s each, in bins) against it (pipeline/satcurve.py; the device tracker
         for "gpu", the host oracle for "cpu"); ``results()`` then also carries ``sat_rows`` / ``sat_curve`` /
-        ``sat_stats`` (satcurve.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
+        ``sat_stats`` (satcurve.RESULT_KEYS). 0: off, nothing is constructed. One GPU only.
+        ``retrieval_sli`` > 0: per service, split TTFT into the retrieval time the trace's first record carries and
+        the model time left, keep both distributions, the requests by TTFT-breach phase and a verdict (retrieval
+        bound, model bound, mixed) over a rolling horizon of that many windows; ``retr_budget_ms`` is retrieval's own
+        budget (None: a quarter of ``ttft_slo_ms``), ``retr_budget_ppm`` the TTFT SLO's error budget, and
+        ``retr_min_requests`` / ``retr_coverage_ppm`` / ``retr_dominance_ppm`` the verdict's thresholds
+        (pipeline/retrsli.py; the device tracker for "gpu", the host oracle for "cpu"); ``results()`` then also
+        carries the ``retr_*`` keys (retrsli.RESULT_KEYS). 0: off, nothing is constructed. One GPU only."""
         from ..ops.engine import model_bytes
 
         self.model_name, self.seed, self.learn = model, seed, learn
@@ -422,9 +431,29 @@ class WindowPipeline:
                 from .satcurve import SaturationOracle
 
                 self.sat = SaturationOracle(**skw)
+        self.retr = None
+        self._retr: Dict[int, Tuple[int, int]] = {}  # buffer -> (window, tracker step)
+        if retrieval_sli:
+            if comm is not None or group is not None or int(shard[1]) > 1:
+                raise ValueError("the retrieval SLI runs on one GPU: no communicator, no sharding "
+                                 "(every GPU's results are gathered on the device)")
+            rkw = dict(span_cap=span_cap, group_cap=group_cap, windows=int(retrieval_sli), n_buffers=self.nb,
+                       slo_ms=ttft_slo_ms,
+                       retrieval_budget_ms=float(ttft_slo_ms) / 4.0 if retr_budget_ms is None else float(retr_budget_ms),
+                       budget_ppm=int(retr_budget_ppm), coverage_ppm=int(retr_coverage_ppm),
+                       dominance_ppm=int(retr_dominance_ppm), min_requests=int(retr_min_requests), device=device)
+            if engine == "gpu":
+                from ..ops.retrsli import RetrievalSliTracker
+
+                self.retr = RetrievalSliTracker(**rkw)
+            else:
+                from .retrsli import RetrievalSliOracle
+
+                self.retr = RetrievalSliOracle(**rkw)
         # the side trackers are fixed from here on: copy_ahead asks once per window and half
         self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
-                                                        self.decode, self.drift, self.errors, self.load, self.sat))
+                                                        self.decode, self.drift, self.errors, self.load, self.sat,
+                                                        self.retr))
 
     def _initial_model(self):
         if self.model_name == "bayes":
@@ -587,6 +616,11 @@ class WindowPipeline:
 
             res = dict(res)
             res.update(sat_keys(self.saturation_results(k, n_groups)))
+        if self.retr is not None:
+            from .retrsli import result_keys as retr_keys
+
+            res = dict(res)
+            res.update(retr_keys(self.retrieval_results(k, n_groups)))
         return res
 
     # ---- open requests (pipeline/openreq.py) ------------------------------------------------
@@ -789,9 +823,29 @@ class WindowPipeline:
 
         return empty_result(n_groups)
 
+    # ---- TTFT phase split (pipeline/retrsli.py) ---------------------------------------------
+    def track_retrieval(self, spans, n_groups: int) -> None:
+        """The retrieval SLI tracker's step for the window about to be submitted: the same span ranges.
+        Every window steps (the horizon is counted in windows)."""
+        if self.retr is None:
+            return
+        self._retr[self.k % self.nb] = (self.k, self.retr.step(list(spans), int(n_groups)))
+
+    def retrieval_results(self, k: int, n_groups: int) -> Dict[str, np.ndarray]:
+        """The retrieval SLI tracker's results of window k (pipeline/retrsli.py RESULT_FIELDS; an empty
+        step's for a window that was submitted past ``track_retrieval``)."""
+        held = self._retr.get(k % self.nb)
+        if held is not None and held[0] == k:
+            return self.retr.results(held[1], n_groups)
+        from .retrsli import empty_result
+
+        return empty_result(n_groups)
+
     def close(self) -> None:
         if self.tracker is not None:
             self.tracker.close()
+        if self.retr is not None:
+            self.retr.close()
         if self.sat is not None:
             self.sat.close()
         if self.load is not None:
@@ -866,6 +920,8 @@ class WindowPipeline:
             self.load.sync()
         if self.sat is not None:
             self.sat.sync()
+        if self.retr is not None:
+            self.retr.sync()
 
     def reset_totals(self) -> None:
         self.eng.reset_totals()
@@ -1195,6 +1251,8 @@ class RingWindowSource:
             pipe.track_load(spans, cut.t_ns, n_groups)
         if pipe.sat is not None:  # the saturation curve sees the window's spans and the cut's time
             pipe.track_saturation(spans, cut.t_ns, n_groups)
+        if pipe.retr is not None:  # the TTFT phase split sees the window's spans
+            pipe.track_retrieval(spans, n_groups)
         t2 = time.perf_counter()
         k = pipe.submit(kern, user, spans, n_groups, labels, cut.bases, with_labels=wl, learn=learn,
                         user_rec=self.user_rec)
