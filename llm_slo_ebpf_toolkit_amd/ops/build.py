@@ -117,7 +117,7 @@ def build_hip_ext(force: bool = False, jobs: int = 4) -> str:
 
 AGENT_KERNELS = ["decode.hip", "join.hip", "posterior.hip", "exchange.hip", "openreq.hip", "slisketch.hip", "exemplars.hip",
                  "podrank.hip", "onset.hip", "decodesli.hip", "drift.hip", "errsli.hip", "loadsli.hip",
-                 "satcurve.hip", "retrsli.hip"]
+                 "satcurve.hip", "retrsli.hip", "steplane.hip"]
 
 
 def build_agent_ext(force: bool = False, jobs: int = 4) -> str:

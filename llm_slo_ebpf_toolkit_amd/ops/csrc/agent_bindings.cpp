@@ -327,12 +327,61 @@ class PyEngine {
   std::unique_ptr<WindowEngine> e_;
 };
 
+// What the bindings of every side tracker share: the tracker itself (gone after close()) and the calls that
+// need nothing of the tracker's own. The GIL is released around everything that can wait for the device.
+template <class T>
+class PyLane {
+ public:
+  explicit PyLane(const char* name) : name_(name) {}
+  T& t() {
+    if (!t_) throw std::logic_error(std::string(name_) + " closed");
+    return *t_;
+  }
+  bool query(int64_t i) { return t().query(i); }
+  // the whole result block of step i as it left the device (uint32 words)
+  py::array_t<uint32_t> block(int64_t i) {
+    T& tr = t();
+    const uint32_t* r;
+    {
+      py::gil_scoped_release nogil;
+      r = tr.results(i);
+    }
+    return copy_array(r, {(py::ssize_t)tr.result_layout().words});
+  }
+  // the tracker's step_ms as a tuple of as many floats
+  py::tuple step_ms(int64_t i) {
+    decltype(std::declval<T&>().step_ms(i)) ms;
+    {
+      py::gil_scoped_release nogil;
+      ms = t().step_ms(i);
+    }
+    return py::tuple(py::cast(ms));
+  }
+  void sync() {
+    py::gil_scoped_release nogil;
+    t().sync();
+  }
+  void close() {
+    if (t_) {
+      py::gil_scoped_release nogil;
+      t_.reset();
+    }
+  }
+
+ protected:
+  std::unique_ptr<T> t_;
+
+ private:
+  const char* name_;
+};
+
 // The open-request tracker (openreq.h): one step per window over the same span ranges the engine
 // gets; results per step index.
-class PyOpenRequests {
+class PyOpenRequests : public PyLane<OpenRequests> {
  public:
   PyOpenRequests(int device, int64_t cap, int span_cap, int group_cap, int n_buffers, double slo_ms, double ttl_ms,
-                 double reorder_ms) {
+                 double reorder_ms)
+      : PyLane("open-request tracker") {
     openreq::Config c;
     c.device = device;
     c.cap = cap;
@@ -345,17 +394,12 @@ class PyOpenRequests {
     openreq::validate(c);
     t_ = std::make_unique<OpenRequests>(c);
   }
-  OpenRequests& t() {
-    if (!t_) throw std::logic_error("open-request tracker closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int64_t prev_cut_ns,
                int n_groups) {
     OpenRequests& tr = t();
     py::gil_scoped_release nogil;
     return tr.step(spans, cut_ns, prev_cut_ns, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     OpenRequests& tr = t();
     if (n_groups < 0 || n_groups > tr.config().group_cap) throw std::invalid_argument("n_groups");
@@ -371,14 +415,6 @@ class PyOpenRequests {
     d["stats"] = copy_array(r + l.stats, {openreq::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::pair<float, float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms.first, ms.second);
-  }
   py::tuple entries() {
     std::vector<uint64_t> k;
     std::vector<int64_t> tt;
@@ -391,26 +427,14 @@ class PyOpenRequests {
     return py::make_tuple(copy_array(k.data(), {n}), copy_array(tt.data(), {n}), copy_array(g.data(), {n}),
                           copy_array(s.data(), {n}));
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<OpenRequests> t_;
 };
 
 // The TTFT sketch (slisketch.h): one step per window over the same span ranges the engine gets;
 // results per step index.
-class PySliSketch {
+class PySliSketch : public PyLane<SliSketch> {
  public:
-  PySliSketch(int device, int span_cap, int group_cap, int windows, int n_buffers) {
+  PySliSketch(int device, int span_cap, int group_cap, int windows, int n_buffers)
+      : PyLane("ttft sketch") {
     slisketch::Config c;
     c.device = device;
     c.span_cap = span_cap;
@@ -420,16 +444,11 @@ class PySliSketch {
     slisketch::validate(c);
     t_ = std::make_unique<SliSketch>(c);
   }
-  SliSketch& t() {
-    if (!t_) throw std::logic_error("ttft sketch closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     SliSketch& sk = t();
     py::gil_scoped_release nogil;
     return sk.step(spans, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     SliSketch& sk = t();
     if (n_groups < 0 || n_groups > sk.config().group_cap) throw std::invalid_argument("n_groups");
@@ -453,26 +472,8 @@ class PySliSketch {
     d["stats"] = copy_array(r + l.stats, {slisketch::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::pair<float, float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms.first, ms.second);
-  }
   py::array_t<uint32_t> rolling() { return rows(true); }
   py::array_t<uint32_t> window_hist() { return rows(false); }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
 
  private:
   py::array_t<uint32_t> rows(bool roll) {
@@ -484,14 +485,14 @@ class PySliSketch {
     }
     return copy_array(h.data(), {sk.config().group_cap, slisketch::kK});
   }
-  std::unique_ptr<SliSketch> t_;
 };
 
 // The request-exemplar tracker (exemplars.h): one step per window over the same span ranges the
 // engine gets; results per step index. Rows leave as bytes [.., 64] (pipeline/exemplars.py EXEMPLAR).
-class PyExemplarTracker {
+class PyExemplarTracker : public PyLane<ExemplarTracker> {
  public:
-  PyExemplarTracker(int device, int k, int windows, int64_t span_cap, int group_cap, int n_buffers, bool lds) {
+  PyExemplarTracker(int device, int k, int windows, int64_t span_cap, int group_cap, int n_buffers, bool lds)
+      : PyLane("request exemplars") {
     if (span_cap < 1 || span_cap >= (int64_t(1) << 31))
       throw std::invalid_argument("request exemplars: span_cap must be in [1, 2^31)");
     exemplars::Config c;
@@ -505,16 +506,11 @@ class PyExemplarTracker {
     exemplars::validate(c);
     t_ = std::make_unique<ExemplarTracker>(c);
   }
-  ExemplarTracker& t() {
-    if (!t_) throw std::logic_error("request exemplars closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     ExemplarTracker& ex = t();
     py::gil_scoped_release nogil;
     return ex.step(spans, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     ExemplarTracker& ex = t();
     if (n_groups < 0 || n_groups > ex.config().group_cap) throw std::invalid_argument("n_groups");
@@ -534,14 +530,6 @@ class PyExemplarTracker {
     d["stats"] = copy_array(r + l.stats, {exemplars::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   py::tuple resident() {
     ExemplarTracker& ex = t();
     std::pair<std::vector<exemplars::Row>, std::vector<uint32_t>> h;
@@ -553,27 +541,15 @@ class PyExemplarTracker {
     return py::make_tuple(copy_array(reinterpret_cast<const uint8_t*>(h.first.data()), {H, G, K, exemplars::kRowBytes}),
                           copy_array(h.second.data(), {H, G}));
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<ExemplarTracker> t_;
 };
 
 // The per-pod breach breakdown (podrank.h): one step per window over the same span ranges the
 // engine gets; results per step index. Rows leave as bytes [.., 32] (pipeline/podrank.py POD_ROW).
-class PyPodRankTracker {
+class PyPodRankTracker : public PyLane<PodRankTracker> {
  public:
   PyPodRankTracker(int device, int k, int windows, int64_t pair_cap, int64_t span_cap, int group_cap, int n_buffers,
-                   double slo_ms, bool lds) {
+                   double slo_ms, bool lds)
+      : PyLane("pod breakdown") {
     if (span_cap < 1 || span_cap >= (int64_t(1) << 31))
       throw std::invalid_argument("pod breakdown: span_cap must be >= 1 and span_cap * windows < 2^22");
     if (pair_cap < 1 || pair_cap > podrank::kMaxPairCap)
@@ -591,16 +567,11 @@ class PyPodRankTracker {
     podrank::validate(c);
     t_ = std::make_unique<PodRankTracker>(c);
   }
-  PodRankTracker& t() {
-    if (!t_) throw std::logic_error("pod breakdown closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     PodRankTracker& pr = t();
     py::gil_scoped_release nogil;
     return pr.step(spans, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     PodRankTracker& pr = t();
     if (n_groups < 0 || n_groups > pr.config().group_cap) throw std::invalid_argument("n_groups");
@@ -625,14 +596,6 @@ class PyPodRankTracker {
     d["stats"] = copy_array(r + l.stats, {podrank::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // per horizon slot: (pair keys u64, n, b, max bits, sum_milli u64)
   py::list resident() {
     PodRankTracker& pr = t();
@@ -650,27 +613,15 @@ class PyPodRankTracker {
     }
     return out;
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<PodRankTracker> t_;
 };
 
 // The breach-onset tracker (onset.h): one step per timed window cut over the same span ranges the
 // engine gets; results per step index. Rows leave as bytes [G, 64] (pipeline/onset.py ONSET_ROW).
-class PyOnsetTracker {
+class PyOnsetTracker : public PyLane<OnsetTracker> {
  public:
   PyOnsetTracker(int device, int64_t bins, int64_t bin_ns, int64_t ref_ppm, int64_t alarm, int64_t span_cap, int group_cap,
-                 int n_buffers, double slo_ms, int64_t ring_records_max, bool lds) {
+                 int n_buffers, double slo_ms, int64_t ring_records_max, bool lds)
+      : PyLane("breach onset") {
     if (bins < onset::kMinBins || bins > onset::kMaxBins)
       throw std::invalid_argument("breach onset: bins must be a power of two in [64, 8192]");
     if (span_cap < 1) throw std::invalid_argument("breach onset: span_cap must be >= 1");
@@ -690,16 +641,11 @@ class PyOnsetTracker {
     onset::validate(c);
     t_ = std::make_unique<OnsetTracker>(c);
   }
-  OnsetTracker& t() {
-    if (!t_) throw std::logic_error("breach onset closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
     OnsetTracker& on = t();
     py::gil_scoped_release nogil;
     return on.step(spans, cut_ns, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     OnsetTracker& on = t();
     if (n_groups < 0 || n_groups > on.config().group_cap) throw std::invalid_argument("n_groups");
@@ -714,14 +660,6 @@ class PyOnsetTracker {
     d["stats"] = copy_array(r + l.stats, {onset::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (cells u64 [group_cap, bins] in slot order, q_hi)
   py::tuple resident() {
     OnsetTracker& on = t();
@@ -734,27 +672,15 @@ class PyOnsetTracker {
                                      {(py::ssize_t)on.config().group_cap, (py::ssize_t)on.config().bins}),
                           h.q_hi);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<OnsetTracker> t_;
 };
 
 // The decode-phase SLI tracker (decodesli.h): one step per window over the same span ranges the
 // engine gets; results per step index (pipeline/decodesli.py RESULT_FIELDS).
-class PyDecodeSliTracker {
+class PyDecodeSliTracker : public PyLane<DecodeSliTracker> {
  public:
   PyDecodeSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double slo_ms,
-                     double tpot_slo_ms, bool lds) {
+                     double tpot_slo_ms, bool lds)
+      : PyLane("decode sli") {
     if (span_cap < 1) throw std::invalid_argument("decode sli: span_cap must be >= 1");
     if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("decode sli: the horizon needs more than 2 GiB");
     decodesli::Config c;
@@ -769,25 +695,10 @@ class PyDecodeSliTracker {
     decodesli::validate(c);
     t_ = std::make_unique<DecodeSliTracker>(c);
   }
-  DecodeSliTracker& t() {
-    if (!t_) throw std::logic_error("decode sli closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     DecodeSliTracker& ds = t();
     py::gil_scoped_release nogil;
     return ds.step(spans, n_groups);
-  }
-  bool query(int64_t i) { return t().query(i); }
-  // the whole result block of step i as it left the device (uint32 words)
-  py::array_t<uint32_t> block(int64_t i) {
-    DecodeSliTracker& ds = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = ds.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)ds.result_layout().words});
   }
   py::dict results(int64_t i, int n_groups) {
     DecodeSliTracker& ds = t();
@@ -809,14 +720,6 @@ class PyDecodeSliTracker {
     d["stats"] = copy_array(r + l.stats, {decodesli::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (rolling rows u32 [group_cap, K], rolling cells u32 [group_cap, 4], rolling sums u64 [group_cap], ring position)
   py::tuple resident() {
     DecodeSliTracker& ds = t();
@@ -829,27 +732,15 @@ class PyDecodeSliTracker {
     return py::make_tuple(copy_array(h.rows.data(), {G, decodesli::kK}), copy_array(h.cells.data(), {G, decodesli::kCells}),
                           copy_array(reinterpret_cast<const uint64_t*>(h.sums.data()), {G}), h.pos);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<DecodeSliTracker> t_;
 };
 
 // The TTFT drift tracker (drift.h): one step per window over the same span ranges the engine gets;
 // results per step index (pipeline/drift.py RESULT_FIELDS).
-class PyDriftTracker {
+class PyDriftTracker : public PyLane<DriftTracker> {
  public:
   PyDriftTracker(int device, int64_t span_cap, int group_cap, int recent, int gap, int baseline, int n_buffers, double crit,
-                 int min_shift, int64_t min_recent, int64_t min_base, int min_base_windows, int64_t hold_max, bool lds) {
+                 int min_shift, int64_t min_recent, int64_t min_base, int min_base_windows, int64_t hold_max, bool lds)
+      : PyLane("ttft drift") {
     if (span_cap < 1) throw std::invalid_argument("ttft drift: span_cap must be >= 1");
     if (span_cap >= (int64_t(1) << 31))
       throw std::invalid_argument("ttft drift: span_cap^2 * recent * baseline must stay below 2^44 (slow_num << 16 would wrap)");
@@ -871,25 +762,10 @@ class PyDriftTracker {
     drift::validate(c);
     t_ = std::make_unique<DriftTracker>(c);
   }
-  DriftTracker& t() {
-    if (!t_) throw std::logic_error("ttft drift closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     DriftTracker& dt = t();
     py::gil_scoped_release nogil;
     return dt.step(spans, n_groups);
-  }
-  bool query(int64_t i) { return t().query(i); }
-  // the whole result block of step i as it left the device (uint32 words)
-  py::array_t<uint32_t> block(int64_t i) {
-    DriftTracker& dt = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = dt.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)dt.result_layout().words});
   }
   py::dict results(int64_t i, int n_groups) {
     DriftTracker& dt = t();
@@ -917,14 +793,6 @@ class PyDriftTracker {
     d["stats"] = copy_array(r + l.stats, {drift::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (recent u32 [group_cap, row stride], base alike, base_fill, base_pos, hold u32 [group_cap], near-ring position)
   py::tuple resident() {
     DriftTracker& dt = t();
@@ -938,19 +806,6 @@ class PyDriftTracker {
                           copy_array(h.base_fill.data(), {G}), copy_array(h.base_pos.data(), {G}),
                           copy_array(h.hold.data(), {G}), h.pos);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<DriftTracker> t_;
 };
 
 // The error SLI tracker (errsli.h): one step per window over the same span ranges the engine gets;
@@ -982,35 +837,21 @@ errsli::Config errsli_config(int device, int64_t span_cap, int group_cap, int wi
   return c;
 }
 
-class PyErrorSliTracker {
+class PyErrorSliTracker : public PyLane<ErrorSliTracker> {
  public:
   PyErrorSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double target,
                     const std::vector<std::tuple<int64_t, int64_t, int64_t>>& pairs, int64_t min_requests, int64_t bad_mask,
-                    bool lds) {
+                    bool lds)
+      : PyLane("error sli") {
     t_ = std::make_unique<ErrorSliTracker>(
         errsli_config(device, span_cap, group_cap, windows, n_buffers, target, pairs, min_requests, bad_mask, lds));
-  }
-  ErrorSliTracker& t() {
-    if (!t_) throw std::logic_error("error sli closed");
-    return *t_;
   }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     ErrorSliTracker& es = t();
     py::gil_scoped_release nogil;
     return es.step(spans, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   uint32_t budget_ppm() { return t().budget_ppm(); }
-  // the whole result block of step i as it left the device (uint32 words)
-  py::array_t<uint32_t> block(int64_t i) {
-    ErrorSliTracker& es = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = es.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)es.result_layout().words});
-  }
   py::dict results(int64_t i, int n_groups) {
     ErrorSliTracker& es = t();
     if (n_groups < 0 || n_groups > es.config().group_cap) throw std::invalid_argument("n_groups");
@@ -1030,14 +871,6 @@ class PyErrorSliTracker {
     d["stats"] = copy_array(r + l.stats, {errsli::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (rolling counts u32 [group_cap, 8], pair sums u32 [group_cap, 4, 4], ages u32 [group_cap], ring position)
   py::tuple resident() {
     ErrorSliTracker& es = t();
@@ -1051,28 +884,16 @@ class PyErrorSliTracker {
                           copy_array(h.sums.data(), {G, errsli::kMaxPairs, errsli::kPairWords}),
                           copy_array(h.age.data(), {G}), h.pos);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<ErrorSliTracker> t_;
 };
 
 // The load SLI tracker (loadsli.h): one step per timed window cut over the same span ranges the
 // engine gets; results per step index. Rows leave as bytes [G, 80] (pipeline/loadsli.py LOAD_ROW).
-class PyLoadSliTracker {
+class PyLoadSliTracker : public PyLane<LoadSliTracker> {
  public:
   PyLoadSliTracker(int device, int64_t bins, int64_t bin_us, int64_t settle_bins, int64_t recent_bins, int64_t min_base_bins,
                    int64_t factor_milli, int64_t min_requests, int64_t min_conc_milli, int64_t span_cap, int group_cap,
-                   int n_buffers, int64_t ring_records_max, bool lds) {
+                   int n_buffers, int64_t ring_records_max, bool lds)
+      : PyLane("load sli") {
     if (bins < loadsli::kMinBins || bins > loadsli::kMaxBins)
       throw std::invalid_argument("load sli: bins must be a power of two in [64, 8192]");
     if (span_cap < 1) throw std::invalid_argument("load sli: span_cap must be >= 1");
@@ -1096,16 +917,11 @@ class PyLoadSliTracker {
     loadsli::validate(c);
     t_ = std::make_unique<LoadSliTracker>(c);
   }
-  LoadSliTracker& t() {
-    if (!t_) throw std::logic_error("load sli closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
     LoadSliTracker& ls = t();
     py::gil_scoped_release nogil;
     return ls.step(spans, cut_ns, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     LoadSliTracker& ls = t();
     if (n_groups < 0 || n_groups > ls.config().group_cap) throw std::invalid_argument("n_groups");
@@ -1121,23 +937,6 @@ class PyLoadSliTracker {
     return d;
   }
   // the step's whole result block, uint32 words
-  py::array_t<uint32_t> block(int64_t i) {
-    LoadSliTracker& ls = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = ls.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)ls.result_layout().words});
-  }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (counts u64, idle_us u64 [group_cap, bins] in slot order, carry, age, previous state, q_hi, q_first)
   py::tuple resident() {
     LoadSliTracker& ls = t();
@@ -1152,29 +951,17 @@ class PyLoadSliTracker {
                           copy_array(h.carry.data(), {G}), copy_array(h.age.data(), {G}),
                           copy_array(h.prev_state.data(), {G}), h.q_hi, h.q_first);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<LoadSliTracker> t_;
 };
 
 // The saturation curve tracker (satcurve.h): one step per timed window cut over the same span ranges
 // the engine gets; results per step index. Rows leave as bytes [G, 64] (pipeline/satcurve.py SAT_ROW),
 // the merged curve as u64 [G, 160, 2].
-class PySaturationTracker {
+class PySaturationTracker : public PyLane<SaturationTracker> {
  public:
   PySaturationTracker(int device, int64_t bins, int64_t bin_us, int64_t settle_bins, int64_t recent_bins, int64_t epoch_bins,
                       int64_t budget_ppm, int64_t min_requests, double slo_ms, int64_t span_cap, int group_cap, int n_buffers,
-                      int64_t ring_records_max, int64_t curve_records_max, bool lds) {
+                      int64_t ring_records_max, int64_t curve_records_max, bool lds)
+      : PyLane("saturation curve") {
     if (bins < satcurve::kMinBins || bins > satcurve::kMaxBins)
       throw std::invalid_argument("saturation curve: bins must be a power of two in [64, 8192]");
     if (span_cap < 1) throw std::invalid_argument("saturation curve: span_cap must be >= 1");
@@ -1199,16 +986,11 @@ class PySaturationTracker {
     satcurve::validate(c);
     t_ = std::make_unique<SaturationTracker>(c);
   }
-  SaturationTracker& t() {
-    if (!t_) throw std::logic_error("saturation curve closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int64_t cut_ns, int n_groups) {
     SaturationTracker& st = t();
     py::gil_scoped_release nogil;
     return st.step(spans, cut_ns, n_groups);
   }
-  bool query(int64_t i) { return t().query(i); }
   py::dict results(int64_t i, int n_groups) {
     SaturationTracker& st = t();
     if (n_groups < 0 || n_groups > st.config().group_cap) throw std::invalid_argument("n_groups");
@@ -1225,23 +1007,6 @@ class PySaturationTracker {
     return d;
   }
   // the step's whole result block, uint32 words
-  py::array_t<uint32_t> block(int64_t i) {
-    SaturationTracker& st = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = st.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)st.result_layout().words});
-  }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (counts, idle_us, sli u64 [group_cap, bins] in slot order, carry, gen u64 [2, group_cap, 160, 2], gen_epoch, age,
   // q_hi, q_first)
   py::tuple resident() {
@@ -1258,28 +1023,16 @@ class PySaturationTracker {
                           copy_array(reinterpret_cast<const uint64_t*>(h.gen.data()), {2, G, satcurve::kK, 2}),
                           py::make_tuple(h.gen_epoch[0], h.gen_epoch[1]), copy_array(h.age.data(), {G}), h.q_hi, h.q_first);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
-
- private:
-  std::unique_ptr<SaturationTracker> t_;
 };
 
 // The TTFT phase split tracker (retrsli.h): one step per window over the same span ranges the engine
 // gets; results per step index (pipeline/retrsli.py RESULT_FIELDS).
-class PyRetrievalSliTracker {
+class PyRetrievalSliTracker : public PyLane<RetrievalSliTracker> {
  public:
   PyRetrievalSliTracker(int device, int64_t span_cap, int group_cap, int windows, int n_buffers, double slo_ms,
                         double retrieval_budget_ms, int64_t budget_ppm, int64_t coverage_ppm, int64_t dominance_ppm,
-                        int64_t min_requests, bool lds) {
+                        int64_t min_requests, bool lds)
+      : PyLane("retrieval sli") {
     if (span_cap < 1) throw std::invalid_argument("retrieval sli: span_cap must be >= 1");
     if (span_cap >= (int64_t(1) << 31)) throw std::invalid_argument("retrieval sli: the horizon needs more than 2 GiB");
     retrsli::Config c;
@@ -1298,25 +1051,10 @@ class PyRetrievalSliTracker {
     retrsli::validate(c);
     t_ = std::make_unique<RetrievalSliTracker>(c);
   }
-  RetrievalSliTracker& t() {
-    if (!t_) throw std::logic_error("retrieval sli closed");
-    return *t_;
-  }
   int64_t step(const std::vector<std::pair<uintptr_t, size_t>>& spans, int n_groups) {
     RetrievalSliTracker& rs = t();
     py::gil_scoped_release nogil;
     return rs.step(spans, n_groups);
-  }
-  bool query(int64_t i) { return t().query(i); }
-  // the whole result block of step i as it left the device (uint32 words)
-  py::array_t<uint32_t> block(int64_t i) {
-    RetrievalSliTracker& rs = t();
-    const uint32_t* r;
-    {
-      py::gil_scoped_release nogil;
-      r = rs.results(i);
-    }
-    return copy_array(r, {(py::ssize_t)rs.result_layout().words});
   }
   py::dict results(int64_t i, int n_groups) {
     RetrievalSliTracker& rs = t();
@@ -1347,14 +1085,6 @@ class PyRetrievalSliTracker {
     d["stats"] = copy_array(r + l.stats, {retrsli::kStats});
     return d;
   }
-  py::tuple step_ms(int64_t i) {
-    std::vector<float> ms;
-    {
-      py::gil_scoped_release nogil;
-      ms = t().step_ms(i);
-    }
-    return py::make_tuple(ms[0], ms[1], ms[2]);
-  }
   // (rolling retrieval rows u32 [group_cap, K], rolling model rows, rolling cells u32 [group_cap, 6], rolling sli u32
   // [group_cap], rolling sums u64 [group_cap, 2], state, age, ring position)
   py::tuple resident() {
@@ -1371,16 +1101,6 @@ class PyRetrievalSliTracker {
                           cut_cells(h.cells.data(), G), sli, copy_array(reinterpret_cast<const uint64_t*>(h.sums.data()), {G, 2}),
                           copy_array(h.state.data(), {G}), copy_array(h.age.data(), {G}), h.pos);
   }
-  void sync() {
-    py::gil_scoped_release nogil;
-    t().sync();
-  }
-  void close() {
-    if (t_) {
-      py::gil_scoped_release nogil;
-      t_.reset();
-    }
-  }
 
  private:
   // [G][kCellStride] words -> the six cells of each row
@@ -1390,8 +1110,6 @@ class PyRetrievalSliTracker {
       std::memcpy(a.mutable_data() + g * retrsli::kCells, p + g * retrsli::kCellStride, retrsli::kCells * sizeof(uint32_t));
     return a;
   }
-
-  std::unique_ptr<RetrievalSliTracker> t_;
 };
 
 py::bytes unique_id() {

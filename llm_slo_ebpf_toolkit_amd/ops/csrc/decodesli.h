@@ -10,17 +10,16 @@
 // streams are not touched. pipeline/decodesli.py holds the same rules in numpy (the oracle, and what
 // the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   observe  one thread per record: an add into its (service, bucket) cell, its (service, table cell)
 //            and the service's 64-bit sum. All requests of a service run one model on one machine, so
 //            their TPOTs share a few buckets: with `lds` every workgroup aggregates in an LDS table
 //            first. Not launched for an empty step,
 //   roll     one wave per service row, every row of group_cap: the window of W steps ago leaves the
 //            rolling row, this one enters and takes its place, the step's row is cleared; the four
-//            ranks of the window's and the rolling row by a wave scan; table and sum roll alike,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            ranks of the window's and the rolling row by a wave scan; table and sum roll alike.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,7 +28,7 @@
 
 #include "decodesli_host.h"
 #include "mislo_common.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -48,26 +47,22 @@ struct Resident {
 class DecodeSliTracker {
  public:
   explicit DecodeSliTracker(const decodesli::Config& cfg);
-  ~DecodeSliTracker();
-  DecodeSliTracker(const DecodeSliTracker&) = delete;
-  DecodeSliTracker& operator=(const DecodeSliTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<decodesli::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (decodesli::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the rolling rows, table and sums and the ring position (synchronous; tests)
   decodesli::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const decodesli::Config& config() const { return cfg_; }
   const decodesli::Layout& result_layout() const { return lay_; }
   uint32_t tpot_slo_us() const { return slo_us_; }
 
  private:
-  int slot_of(int64_t i) const;
   // row `which` of the state: [0, W) the horizon's windows, W the rolling row, W + 1 this step's
   uint32_t* hist(size_t which) const { return hist_ + which * (size_t)cfg_.group_cap * decodesli::kK; }
   uint32_t* cells(size_t which) const { return cells_ + which * (size_t)cfg_.group_cap * decodesli::kCells; }
@@ -75,16 +70,11 @@ class DecodeSliTracker {
 
   decodesli::Config cfg_;
   decodesli::Layout lay_;
-  openreq::SlotRing slots_;
   uint32_t slo_us_ = 0;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
-  uint32_t* hist_ = nullptr;
+  StepLane lane_;
+  uint32_t* hist_ = nullptr;  // the lane's, like the two below
   uint32_t* cells_ = nullptr;
   unsigned long long* sum_ = nullptr;
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

@@ -15,6 +15,7 @@
 
 #include "onset_host.h"      // lds_hash, kLdsSlots, kLdsProbes: the observe kernel's table is onset's
 #include "slisketch_host.h"  // rank_of, quantile_permille, kQuantiles, kEmpty
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace decodesli {
@@ -29,7 +30,6 @@ constexpr int kK = 336;                          // buckets: 16 exact ones, then
 constexpr int kPerLane = 6;                      // 56 lanes x 6 consecutive buckets
 constexpr int kRowLanes = kK / kPerLane;
 constexpr int kCells = 4;                        // the table (TTFT breach, TPOT breach): cell = tb + 2 db
-constexpr int kSpanBytes = 64;                   // collector/records.py SPAN
 constexpr int kLdsSlots = onset::kLdsSlots;
 constexpr int kLdsProbes = onset::kLdsProbes;
 static_assert(kRowLanes * kPerLane == kK && kRowLanes <= 64 && kK % 4 == 0, "a row is 6 buckets per lane of one wave");
@@ -128,19 +128,9 @@ inline void validate(const Config& c) {
   if (device_bytes(c) > (uint64_t(1) << 31)) throw std::invalid_argument("decode sli: the horizon needs more than 2 GiB");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("decode sli step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("decode sli step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("decode sli step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "decode sli");
 }
 
 inline void check_step(int n_groups, int group_cap) {

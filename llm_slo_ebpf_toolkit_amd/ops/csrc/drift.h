@@ -10,16 +10,15 @@
 // (slisketch_host.h). The engine, its graphs and its streams are not touched. pipeline/drift.py holds
 // the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   observe  one thread per record: an add into its (service, bucket) cell of the step's row. One
 //            service's TTFTs share few buckets: with `lds` every workgroup aggregates in an LDS table
 //            first. Not launched for an empty step,
 //   roll     one wave per service row, every row of group_cap: the three ring updates, two wave scans,
 //            the two cross-multiplied maxima with their first bucket, the ranks, then lane 0 decides,
-//            counts the hold and drops the baseline when it is reached,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            counts the hold and drops the baseline when it is reached.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +27,7 @@
 
 #include "drift_host.h"
 #include "mislo_common.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -57,38 +56,29 @@ struct Words {
 class DriftTracker {
  public:
   explicit DriftTracker(const drift::Config& cfg);
-  ~DriftTracker();
-  DriftTracker(const DriftTracker&) = delete;
-  DriftTracker& operator=(const DriftTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<drift::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (drift::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the recent and baseline rows, fill, position, hold and the ring position (synchronous; tests)
   drift::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const drift::Config& config() const { return cfg_; }
   const drift::Layout& result_layout() const { return lay_; }
 
  private:
-  int slot_of(int64_t i) const;
   // row `which` of the state: [0, R + L) the near ring, then recent, base, this step's, base_ring[B]
   uint32_t* row(size_t which) const { return hist_ + which * (size_t)cfg_.group_cap * drift::kRowStride; }
 
   drift::Config cfg_;
   drift::Layout lay_;
-  openreq::SlotRing slots_;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
-  uint32_t* hist_ = nullptr;
+  StepLane lane_;
+  uint32_t* hist_ = nullptr;   // the lane's, like words_
   uint32_t* words_ = nullptr;  // [4][group_cap]: drift::Words
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

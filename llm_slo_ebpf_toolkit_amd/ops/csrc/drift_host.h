@@ -16,6 +16,7 @@
 
 #include "onset_host.h"      // lds_hash, kLdsSlots, kLdsProbes: the observe kernel's table is onset's
 #include "slisketch_host.h"  // bucket_of_bits, rank_of, quantile_permille, kK, kRowStride, kPerLane, kEmpty
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace drift {
@@ -25,7 +26,6 @@ using slisketch::kK;
 using slisketch::kPerLane;
 using slisketch::kQuantiles;
 using slisketch::kRowStride;
-using slisketch::kSpanBytes;
 
 constexpr int kRowLanes = kRowStride / kPerLane;  // lanes of the roll kernel's wave that own buckets
 constexpr int kLdsSlots = onset::kLdsSlots;
@@ -182,19 +182,9 @@ inline void validate(const Config& c) {
   if (device_bytes(c) > (uint64_t(1) << 31)) throw std::invalid_argument("ttft drift: the rings need more than 2 GiB");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("ttft drift step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("ttft drift step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("ttft drift step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "ttft drift");
 }
 
 inline void check_step(int n_groups, int group_cap) {

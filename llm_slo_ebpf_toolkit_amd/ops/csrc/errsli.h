@@ -9,17 +9,16 @@
 // streams are not touched. pipeline/errsli.py holds the same rules in numpy (the oracle, and what the
 // CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots and the publish). One step per window, between the
+// lane's copy and its publish:
 //   observe  one thread per record: an add into its (service, class) cell. A service's requests fall
 //            into one or two classes, so with `lds` every workgroup aggregates in an LDS table first.
 //            Not launched for an empty step,
 //   roll     one wave per service row, every row of group_cap: lanes 0-7 roll the class counts (the
 //            window of W steps ago leaves, this one enters and takes its place, the step's row is
 //            cleared), lanes 8-15 each keep one pair window's rolling (n, bad) and compare it; a ballot
-//            gives the firing pairs,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            gives the firing pairs.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,7 +27,7 @@
 
 #include "errsli_host.h"
 #include "mislo_common.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -47,41 +46,32 @@ struct Resident {
 class ErrorSliTracker {
  public:
   explicit ErrorSliTracker(const errsli::Config& cfg);
-  ~ErrorSliTracker();
-  ErrorSliTracker(const ErrorSliTracker&) = delete;
-  ErrorSliTracker& operator=(const ErrorSliTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<errsli::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (errsli::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the rolling counts, the pairs' sums, the ages and the ring position (synchronous; tests)
   errsli::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const errsli::Config& config() const { return cfg_; }
   const errsli::Layout& result_layout() const { return lay_; }
   uint32_t budget_ppm() const { return budget_; }
 
  private:
-  int slot_of(int64_t i) const;
   // row `which` of the state: [0, W) the horizon's windows, W the rolling row, W + 1 this step's
   uint32_t* row(size_t which) const { return rows_ + which * (size_t)cfg_.group_cap * errsli::kRowWords; }
 
   errsli::Config cfg_;
   errsli::Layout lay_;
-  openreq::SlotRing slots_;
   uint32_t budget_ = 0;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
-  uint32_t* rows_ = nullptr;
+  StepLane lane_;
+  uint32_t* rows_ = nullptr;  // the lane's, like the two below
   uint32_t* sums_ = nullptr;  // [group_cap][4][4]
   uint32_t* age_ = nullptr;   // [group_cap]
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

@@ -10,13 +10,6 @@ namespace errsli {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -164,96 +157,43 @@ __global__ __launch_bounds__(kNT) void k_err_roll(uint32_t* __restrict__ cur, ui
   }
 }
 
-// the step's result block into its pinned host block; the block cleared for the next step
-__global__ __launch_bounds__(kNT) void k_err_publish(uint4* __restrict__ block, uint4* __restrict__ host, size_t n16) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = block[i];
-    block[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 }  // namespace errsli
 
 using namespace errsli;
 
-ErrorSliTracker::ErrorSliTracker(const Config& cfg) : cfg_(cfg), slots_(cfg.n_buffers) {
-  validate(cfg);
-  lay_ = layout(cfg.group_cap);
+ErrorSliTracker::ErrorSliTracker(const Config& cfg)
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap)),
+      lane_("error sli", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
   budget_ = errsli::budget_ppm(cfg.target);
   const size_t rows = (size_t)cfg.windows + 2, G = (size_t)cfg.group_cap;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&rows_), rows * G * kRowWords * 4));
-  HIPCHECK(hipMemsetAsync(rows_, 0, rows * G * kRowWords * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&sums_), G * kSumWords * 4));
-  HIPCHECK(hipMemsetAsync(sums_, 0, G * kSumWords * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&age_), G * 4));
-  HIPCHECK(hipMemsetAsync(age_, 0, G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    for (auto* v : {&ev_begin_, &ev_copied_, &ev_observed_, &ev_end_}) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      v->push_back(e);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-ErrorSliTracker::~ErrorSliTracker() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(spans_);
-  (void)hipFree(rows_);
-  (void)hipFree(sums_);
-  (void)hipFree(age_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_observed_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  rows_ = lane_.zeroed<uint32_t>(rows * G * kRowWords);
+  sums_ = lane_.zeroed<uint32_t>(G * kSumWords);
+  age_ = lane_.zeroed<uint32_t>(G);
+  lane_.ready();
 }
 
 int64_t ErrorSliTracker::step(const std::vector<Range>& spans, int n_groups) {
   check_step(n_groups, cfg_.group_cap);
   const size_t n = plan_ranges(spans, cfg_.span_cap);
   // nothing has changed up to here
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
   const int64_t W = cfg_.windows;
   const size_t at = (size_t)(idx % W);
   uint32_t* cur = row((size_t)W + 1);
   const dim3 block(kNT);
   if (n) {
     const dim3 og(grid_for((int64_t)n, kNT, 1024));
-    uint32_t* stats = block_ + lay_.stats;
+    uint32_t* stats = blk + lay_.stats;
     if (cfg_.lds)
-      hipLaunchKernelGGL(k_err_observe<true>, og, block, 0, st_, spans_, (int)n, n_groups, cur, stats);
+      hipLaunchKernelGGL(k_err_observe<true>, og, block, 0, st, lane_.spans(), (int)n, n_groups, cur, stats);
     else
-      hipLaunchKernelGGL(k_err_observe<false>, og, block, 0, st_, spans_, (int)n, n_groups, cur, stats);
+      hipLaunchKernelGGL(k_err_observe<false>, og, block, 0, st, lane_.spans(), (int)n, n_groups, cur, stats);
   }
-  HIPCHECK(hipEventRecord(ev_observed_[s], st_));
+  lane_.mark(s, StepLane::kObserved);
   RollArgs a{};
   a.n_pairs = (uint32_t)cfg_.pairs.size();
   a.min_requests = (uint32_t)cfg_.min_requests;
@@ -264,58 +204,22 @@ int64_t ErrorSliTracker::step(const std::vector<Range>& spans, int n_groups) {
     // the step x before this one filled row (idx - x) % W, and nothing has replaced it since (x <= W)
     for (int k = 0; k < 2; ++k) a.leave[2 * p + k] = idx >= x[k] ? row((size_t)((idx - x[k]) % W)) : nullptr;
   }
-  hipLaunchKernelGGL(k_err_roll, dim3(grid_for(cfg_.group_cap, kRowsPerBlock, 1 << 20)), block, 0, st_, cur, row(at),
-                     row((size_t)W), sums_, age_, block_, lay_, a, cfg_.group_cap);
-  const size_t n16 = lay_.words / 4;
-  hipLaunchKernelGGL(k_err_publish, dim3(grid_for((int64_t)n16, kNT, 64)), block, 0, st_,
-                     reinterpret_cast<uint4*>(block_), reinterpret_cast<uint4*>(host_[s]), n16);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  hipLaunchKernelGGL(k_err_roll, dim3(grid_for(cfg_.group_cap, kRowsPerBlock, 1 << 20)), block, 0, st, cur, row(at),
+                     row((size_t)W), sums_, age_, blk, lay_, a, cfg_.group_cap);
+  lane_.publish(s, 64);
   return idx;
 }
 
-int ErrorSliTracker::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("error sli step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool ErrorSliTracker::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* ErrorSliTracker::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::vector<float> ErrorSliTracker::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f, obs = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&obs, ev_copied_[s], ev_observed_[s]));
-  return {all, kern, obs};
-}
-
-void ErrorSliTracker::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd),
+          lane_.ms(i, StepLane::kCopied, StepLane::kObserved)};
 }
 
 Resident ErrorSliTracker::resident() {
   sync();
   const size_t W = (size_t)cfg_.windows, G = (size_t)cfg_.group_cap;
   Resident out;
-  out.pos = slots_.next() % (int64_t)W;
+  out.pos = lane_.steps() % (int64_t)W;
   out.counts.resize(G * kRowWords);
   out.sums.resize(G * kSumWords);
   out.age.resize(G);

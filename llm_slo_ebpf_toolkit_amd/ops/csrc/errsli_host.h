@@ -15,6 +15,7 @@
 
 #include "onset_host.h"      // lds_hash, kLdsSlots, kLdsProbes: the observe kernel's table is onset's
 #include "slisketch_host.h"  // MISLO_SK_HD
+#include "steplane_host.h"   // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace errsli {
@@ -29,7 +30,6 @@ constexpr int kPairLane0 = kClasses;       // the roll kernel's lane 8 + 2 p + w
 constexpr uint32_t kBadAllowed = 0xFEu;    // ok can never burn the budget
 constexpr uint32_t kBadDefault = 0xF8u;    // throttled, timeout, unavailable, server, other
 constexpr uint64_t kBurnScale = 1000000000ull;  // factor_milli * budget_ppm is in 10^-9
-constexpr int kSpanBytes = 64;             // collector/records.py SPAN
 constexpr int kLdsSlots = onset::kLdsSlots;
 constexpr int kLdsProbes = onset::kLdsProbes;
 
@@ -140,19 +140,9 @@ inline void validate(const Config& c) {
   if (device_bytes(c) > (uint64_t(1) << 31)) throw std::invalid_argument("error sli: the horizon needs more than 2 GiB");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("error sli step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("error sli step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("error sli step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "error sli");
 }
 
 inline void check_step(int n_groups, int group_cap) {

@@ -9,15 +9,14 @@
 // and its streams are not touched. pipeline/exemplars.py holds the same rules in numpy (the oracle,
 // and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   select   one thread per record: the key cascades into the group's K sorted slots by atomicMax
 //            (integer atomics only), privatised in LDS for the groups below kLdsGroups,
 //   merge    one wave per service row, every row of group_cap: lanes < K gather the window's rows
 //            from the span buffer into the horizon's slot step % H and the block, the wave ranks the
-//            H * K resident candidates and writes the K best with their age,
-//   publish  the step's result block into its pinned host block (vector stores) and clear it.
+//            H * K resident candidates and writes the K best with their age.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,7 +25,7 @@
 
 #include "exemplars_host.h"
 #include "mislo_common.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -37,47 +36,37 @@ void launch_select(const Span* sp, int n, int n_groups, int k, bool lds, unsigne
                    uint32_t* stats, hipStream_t st);
 void launch_merge(const Span* sp, int n, unsigned long long* keys, uint32_t* count, Row* horizon, uint32_t* held,
                   uint32_t* block, Layout lay, int group_cap, int k, int windows, int cur, hipStream_t st);
-void launch_publish(uint32_t* block, uint32_t* host, size_t words, hipStream_t st);
 
 }  // namespace exemplars
 
 class ExemplarTracker {
  public:
   explicit ExemplarTracker(const exemplars::Config& cfg);
-  ~ExemplarTracker();
-  ExemplarTracker(const ExemplarTracker&) = delete;
-  ExemplarTracker& operator=(const ExemplarTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<exemplars::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (exemplars::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the select kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the horizon's rows [windows][group_cap][k] and their valid counts [windows][group_cap]
   // (synchronous; tests)
   std::pair<std::vector<exemplars::Row>, std::vector<uint32_t>> resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const exemplars::Config& config() const { return cfg_; }
   const exemplars::Layout& result_layout() const { return lay_; }
-  int64_t steps() const { return slots_.next(); }
+  int64_t steps() const { return lane_.steps(); }
 
  private:
-  int slot_of(int64_t i) const;
-
   exemplars::Config cfg_;
   exemplars::Layout lay_;
-  openreq::SlotRing slots_;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
+  StepLane lane_;
+  // the lane's
   unsigned long long* keys_ = nullptr;  // [group_cap][k] the step's sorted slots, 0 = empty
   uint32_t* count_ = nullptr;           // [group_cap] records observed in the step
   exemplars::Row* horizon_ = nullptr;   // [windows][group_cap][k]
   uint32_t* held_ = nullptr;            // [windows][group_cap] valid rows
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_selected_, ev_end_;
 };
 
 }  // namespace mislo

@@ -10,13 +10,6 @@ namespace exemplars {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -176,19 +169,6 @@ __global__ __launch_bounds__(kNT) void k_exemplar_merge(const Span* __restrict__
   }
 }
 
-// the step's result block into its pinned host block, and cleared for the next step
-__global__ __launch_bounds__(kNT) void k_exemplar_publish(uint4* __restrict__ block, uint4* __restrict__ host,
-                                                          size_t n16) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = block[i];
-    block[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 
 void launch_select(const Span* sp, int n, int n_groups, int k, bool lds, u64* keys, uint32_t* count, uint32_t* stats,
@@ -207,122 +187,39 @@ void launch_merge(const Span* sp, int n, u64* keys, uint32_t* count, Row* horizo
                      count, horizon, held, block, lay, group_cap, k, windows, cur);
 }
 
-void launch_publish(uint32_t* block, uint32_t* host, size_t words, hipStream_t st) {
-  const size_t n16 = words / 4;
-  hipLaunchKernelGGL(k_exemplar_publish, dim3(grid_for((int64_t)n16, kNT, 64)), dim3(kNT), 0, st,
-                     reinterpret_cast<uint4*>(block), reinterpret_cast<uint4*>(host), n16);
-}
-
 }  // namespace exemplars
 
 using namespace exemplars;
 
 ExemplarTracker::ExemplarTracker(const Config& cfg)
-    : cfg_(cfg), lay_(layout(cfg.group_cap, cfg.k)), slots_(cfg.n_buffers) {
-  validate(cfg);
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap, cfg.k)),
+      lane_("request exemplars", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
   const size_t G = (size_t)cfg.group_cap, K = (size_t)cfg.k, H = (size_t)cfg.windows;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&keys_), G * K * 8));
-  HIPCHECK(hipMemsetAsync(keys_, 0, G * K * 8, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&count_), G * 4));
-  HIPCHECK(hipMemsetAsync(count_, 0, G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&horizon_), H * G * K * sizeof(Row)));
-  HIPCHECK(hipMemsetAsync(horizon_, 0, H * G * K * sizeof(Row), st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&held_), H * G * 4));
-  HIPCHECK(hipMemsetAsync(held_, 0, H * G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    for (auto* v : {&ev_begin_, &ev_copied_, &ev_selected_, &ev_end_}) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      v->push_back(e);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-ExemplarTracker::~ExemplarTracker() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(spans_);
-  (void)hipFree(keys_);
-  (void)hipFree(count_);
-  (void)hipFree(horizon_);
-  (void)hipFree(held_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_selected_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  keys_ = lane_.zeroed<unsigned long long>(G * K);
+  count_ = lane_.zeroed<uint32_t>(G);
+  horizon_ = lane_.zeroed<Row>(H * G * K);
+  held_ = lane_.zeroed<uint32_t>(H * G);
+  lane_.ready();
 }
 
 int64_t ExemplarTracker::step(const std::vector<Range>& spans, int n_groups) {
   check_step(n_groups, cfg_.group_cap);
   const size_t n = plan_ranges(spans, cfg_.span_cap);
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
-  launch_select(spans_, (int)n, n_groups, cfg_.k, cfg_.lds, keys_, count_, block_ + lay_.stats, st_);
-  HIPCHECK(hipEventRecord(ev_selected_[s], st_));
-  launch_merge(spans_, (int)n, keys_, count_, horizon_, held_, block_, lay_, cfg_.group_cap, cfg_.k, cfg_.windows,
-               (int)(idx % (int64_t)cfg_.windows), st_);
-  launch_publish(block_, host_[s], lay_.words, st_);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
+  launch_select(lane_.spans(), (int)n, n_groups, cfg_.k, cfg_.lds, keys_, count_, blk + lay_.stats, st);
+  lane_.mark(s, StepLane::kObserved);  // the select kernel is this tracker's observe
+  launch_merge(lane_.spans(), (int)n, keys_, count_, horizon_, held_, blk, lay_, cfg_.group_cap, cfg_.k, cfg_.windows,
+               (int)(idx % (int64_t)cfg_.windows), st);
+  lane_.publish(s, 64);
   return idx;
 }
 
-int ExemplarTracker::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("request exemplars step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool ExemplarTracker::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* ExemplarTracker::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::vector<float> ExemplarTracker::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f, sel = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&sel, ev_copied_[s], ev_selected_[s]));
-  return {all, kern, sel};
-}
-
-void ExemplarTracker::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd),
+          lane_.ms(i, StepLane::kCopied, StepLane::kObserved)};
 }
 
 std::pair<std::vector<Row>, std::vector<uint32_t>> ExemplarTracker::resident() {

@@ -13,6 +13,8 @@
 #include <utility>
 #include <vector>
 
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
+
 #if defined(__HIPCC__)
 #define MISLO_EX_HD __host__ __device__
 #else
@@ -25,7 +27,6 @@ namespace exemplars {
 constexpr int kMaxK = 8;        // exemplars per service and list
 constexpr int kMaxH = 16;       // windows of the horizon: H * K <= 128 = two candidates per lane of one wave
 constexpr int kLdsGroups = 64;  // groups whose K slots the select kernel keeps in LDS ([64][8] u64 = 4 KB)
-constexpr int kSpanBytes = 64;  // collector/records.py SPAN
 constexpr int kRowBytes = 64;
 constexpr int kRowWords = kRowBytes / 4;
 
@@ -117,20 +118,9 @@ inline Layout layout(int group_cap, int k) {
   return l;
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("request exemplars step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("request exemplars step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n)
-      throw std::invalid_argument("request exemplars step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "request exemplars");
 }
 
 inline void check_step(int n_groups, int group_cap) {

@@ -11,16 +11,15 @@
 // device agree bit for bit. The engine, its graphs and its streams are not touched.
 // pipeline/loadsli.py holds the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window with a timed cut:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window with a timed cut, between the
+// lane's copy and its publish:
 //   advance  one wave per row: fold the evicted bins' starts - ends into carry and clear their slots;
 //            not launched when q_hi did not move,
 //   observe  one thread per record, at most two cell updates; with `lds` every workgroup aggregates
 //            its cells, carry increments and statistics in an LDS table first,
 //   scan     one wave per service row, every row of group_cap: a wave scan of starts - ends, then the
-//            three ranges' sums and the peak in one pass; lane 0 classifies and stores the row,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            three ranges' sums and the peak in one pass; lane 0 classifies and stores the row.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,7 +28,7 @@
 
 #include "loadsli_host.h"
 #include "mislo_common.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -48,41 +47,32 @@ struct Resident {
 class LoadSliTracker {
  public:
   explicit LoadSliTracker(const loadsli::Config& cfg);
-  ~LoadSliTracker();
-  LoadSliTracker(const LoadSliTracker&) = delete;
-  LoadSliTracker& operator=(const LoadSliTracker&) = delete;
 
   // One window cut at cut_ns (> 0); returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<loadsli::Range>& spans, int64_t cut_ns, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (loadsli::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the ring and what goes with it (synchronous; tests)
   loadsli::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   int64_t q_hi() const { return q_hi_; }
   const loadsli::Config& config() const { return cfg_; }
   const loadsli::Layout& result_layout() const { return lay_; }
 
  private:
-  int slot_of(int64_t i) const;
-
   loadsli::Config cfg_;
   loadsli::Layout lay_;
-  openreq::SlotRing slots_;
   loadsli::Population pop_;
   int64_t q_hi_ = loadsli::kNoBin, q_first_ = loadsli::kNoBin;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
+  StepLane lane_;
+  // the lane's
   unsigned long long* counts_ = nullptr;  // [group_cap][bins]
   unsigned long long* idle_ = nullptr;    // [group_cap][bins]
   int32_t* carry_ = nullptr;              // [group_cap]
   uint32_t* age_ = nullptr;               // [group_cap] age, then [group_cap] previous state
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_advanced_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

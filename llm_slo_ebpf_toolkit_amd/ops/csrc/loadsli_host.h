@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "onset_host.h"
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace loadsli {
@@ -43,7 +44,6 @@ constexpr int64_t kMaxProduct = int64_t(1) << 53;  // ring_records_max * bins * 
 constexpr int64_t kMinFactorMilli = 1001, kMaxFactorMilli = 64000;
 constexpr int64_t kMaxMinRequests = 2147483647ll;
 constexpr int64_t kMaxMinConcMilli = 1000000000ll;
-constexpr int kSpanBytes = 64;  // collector/records.py SPAN
 constexpr int kRowBytes = 80;
 constexpr int kRowWords = kRowBytes / 4;
 // records that do not end a request: first-token records (bit 2) and start records (bit 3)
@@ -262,19 +262,9 @@ inline void validate(const Config& c) {
     throw std::invalid_argument("load sli: ring_records_max * bins * bin_us must be in [1, 2^53], ring_records_max <= 2^31 - 1");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("load sli step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("load sli step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("load sli step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "load sli");
 }
 
 inline void check_step(int64_t cut_ns, int n_groups, int group_cap) {

@@ -11,16 +11,15 @@
 // agree bit for bit. The engine, its graphs and its streams are not touched. pipeline/onset.py holds
 // the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window with a timed cut:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window with a timed cut, between the
+// lane's copy and its publish:
 //   advance  clear the slots of the bins (previous q_hi, q_hi] in every row; not launched when q_hi
 //            did not move,
 //   observe  one thread per record: one 64-bit add into its (service, slot) cell; with `lds` every
 //            workgroup aggregates its cells in an LDS table first,
 //   scan     one wave per service row, every row of group_cap: the CUSUM as a wave scan of
-//            (sum, minimum prefix) pairs (onset_host.h combine), then onset, alarm, peak and counts,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            (sum, minimum prefix) pairs (onset_host.h combine), then onset, alarm, peak and counts.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,7 +28,7 @@
 
 #include "mislo_common.h"
 #include "onset_host.h"
-#include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -46,38 +45,28 @@ struct Resident {
 class OnsetTracker {
  public:
   explicit OnsetTracker(const onset::Config& cfg);
-  ~OnsetTracker();
-  OnsetTracker(const OnsetTracker&) = delete;
-  OnsetTracker& operator=(const OnsetTracker&) = delete;
 
   // One window cut at cut_ns (> 0); returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<onset::Range>& spans, int64_t cut_ns, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (onset::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the ring and q_hi (synchronous; tests)
   onset::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   int64_t q_hi() const { return q_hi_; }
   const onset::Config& config() const { return cfg_; }
   const onset::Layout& result_layout() const { return lay_; }
 
  private:
-  int slot_of(int64_t i) const;
-
   onset::Config cfg_;
   onset::Layout lay_;
-  openreq::SlotRing slots_;
   onset::Population pop_;
   int64_t q_hi_ = onset::kNoBin;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
-  unsigned long long* ring_ = nullptr;  // [group_cap][bins] cells
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_advanced_, ev_observed_, ev_end_;
+  StepLane lane_;
+  unsigned long long* ring_ = nullptr;  // [group_cap][bins] cells, the lane's
 };
 
 }  // namespace mislo

@@ -10,13 +10,6 @@ namespace onset {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -190,59 +183,18 @@ __global__ __launch_bounds__(kNT) void k_onset_scan(const u64* __restrict__ ring
   }
 }
 
-// the step's result block into its pinned host block; the block cleared for the next step
-__global__ __launch_bounds__(kNT) void k_onset_publish(uint4* __restrict__ block, uint4* __restrict__ host, size_t n16) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = block[i];
-    block[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 }  // namespace onset
 
 using namespace onset;
 
 OnsetTracker::OnsetTracker(const Config& cfg)
-    : cfg_(cfg), slots_(cfg.n_buffers), pop_((uint32_t)cfg.bins, cfg.ring_records_max) {
-  validate(cfg);
-  lay_ = layout(cfg.group_cap);
-  const size_t cells = (size_t)cfg.group_cap * (size_t)cfg.bins;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&ring_), cells * 8));
-  HIPCHECK(hipMemsetAsync(ring_, 0, cells * 8, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    for (auto* v : {&ev_begin_, &ev_copied_, &ev_advanced_, &ev_observed_, &ev_end_}) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      v->push_back(e);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-OnsetTracker::~OnsetTracker() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(spans_);
-  (void)hipFree(ring_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_advanced_, &ev_observed_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap)),
+      pop_((uint32_t)cfg.bins, cfg.ring_records_max),
+      lane_("breach onset", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 2) {
+  ring_ = lane_.zeroed<unsigned long long>((size_t)cfg.group_cap * (size_t)cfg.bins);
+  lane_.ready();
 }
 
 int64_t OnsetTracker::step(const std::vector<Range>& spans, int64_t cut_ns, int n_groups) {
@@ -253,84 +205,39 @@ int64_t OnsetTracker::step(const std::vector<Range>& spans, int64_t cut_ns, int 
   // nothing has changed up to here
   pop_.take(q_hi, n);
   q_hi_ = q_hi;
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
   const int G = cfg_.group_cap;
   const uint32_t bins = (uint32_t)cfg_.bins;
-  uint32_t* stats = block_ + lay_.stats;
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
+  uint32_t* stats = blk + lay_.stats;
   const dim3 block(kNT);
   if (q_hi > prev) {
     const uint32_t count = cleared(prev, q_hi, bins);
-    hipLaunchKernelGGL(k_onset_advance, dim3(grid_for((int64_t)G * count, kNT, 1024)), block, 0, st_, ring_, G, bins, prev,
+    hipLaunchKernelGGL(k_onset_advance, dim3(grid_for((int64_t)G * count, kNT, 1024)), block, 0, st, ring_, G, bins, prev,
                        count);
   }
-  HIPCHECK(hipEventRecord(ev_advanced_[s], st_));
+  lane_.mark(s, StepLane::kAdvanced);
   if (n) {
     const dim3 og(grid_for((int64_t)n, kNT, 1024));
     const float slo = (float)cfg_.slo_ms;
     if (cfg_.lds)
-      hipLaunchKernelGGL(k_onset_observe<true>, og, block, 0, st_, spans_, (int)n, n_groups, slo, cfg_.bin_ns, q_hi, bins,
-                         ring_, stats);
+      hipLaunchKernelGGL(k_onset_observe<true>, og, block, 0, st, lane_.spans(), (int)n, n_groups, slo, cfg_.bin_ns, q_hi,
+                         bins, ring_, stats);
     else
-      hipLaunchKernelGGL(k_onset_observe<false>, og, block, 0, st_, spans_, (int)n, n_groups, slo, cfg_.bin_ns, q_hi, bins,
-                         ring_, stats);
+      hipLaunchKernelGGL(k_onset_observe<false>, og, block, 0, st, lane_.spans(), (int)n, n_groups, slo, cfg_.bin_ns, q_hi,
+                         bins, ring_, stats);
   }
-  HIPCHECK(hipEventRecord(ev_observed_[s], st_));
-  hipLaunchKernelGGL(k_onset_scan, dim3(grid_for(G, kRowsPerBlock, 1 << 20)), block, 0, st_, ring_, bins, q_hi, cfg_.ref_ppm,
-                     cfg_.alarm * kMillion, block_, lay_.rows, G);
-  const size_t n16 = lay_.words / 4;
-  hipLaunchKernelGGL(k_onset_publish, dim3(grid_for((int64_t)n16, kNT, 1024)), block, 0, st_,
-                     reinterpret_cast<uint4*>(block_), reinterpret_cast<uint4*>(host_[s]), n16);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  lane_.mark(s, StepLane::kObserved);
+  hipLaunchKernelGGL(k_onset_scan, dim3(grid_for(G, kRowsPerBlock, 1 << 20)), block, 0, st, ring_, bins, q_hi, cfg_.ref_ppm,
+                     cfg_.alarm * kMillion, blk, lay_.rows, G);
+  lane_.publish(s, 1024);
   return idx;
 }
 
-int OnsetTracker::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("breach onset step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool OnsetTracker::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* OnsetTracker::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::vector<float> OnsetTracker::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f, obs = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&obs, ev_advanced_[s], ev_observed_[s]));
-  return {all, kern, obs};
-}
-
-void OnsetTracker::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd),
+          lane_.ms(i, StepLane::kAdvanced, StepLane::kObserved)};
 }
 
 Resident OnsetTracker::resident() {

@@ -14,6 +14,8 @@
 #include <utility>
 #include <vector>
 
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
+
 #if defined(__HIPCC__)
 #define MISLO_ON_HD __host__ __device__
 #else
@@ -29,7 +31,6 @@ constexpr int64_t kMinBinNs = 1000000ll;
 constexpr int64_t kMaxBinNs = 60000000000ll;
 constexpr int64_t kMillion = 1000000ll;  // the CUSUM counts in millionths of a breach
 constexpr int64_t kMaxRingRecords = 2147483647ll;  // 2^31 - 1: a cell's request count cannot carry into its breaches
-constexpr int kSpanBytes = 64;         // collector/records.py SPAN
 constexpr int kRowBytes = 64;
 constexpr int kRowWords = kRowBytes / 4;
 constexpr int kLdsSlots = 256;         // the observe kernel's per-workgroup table (16 B a slot, 4 KB)
@@ -174,19 +175,9 @@ inline void validate(const Config& c) {
     throw std::invalid_argument("breach onset: ring_records_max must be in [1, 2^31 - 1]");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("breach onset step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("breach onset step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("breach onset step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "breach onset");
 }
 
 inline void check_step(int64_t cut_ns, int n_groups, int group_cap) {

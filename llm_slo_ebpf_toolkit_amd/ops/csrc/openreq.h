@@ -8,16 +8,15 @@
 // host); the engine, its graphs and its streams are not touched. pipeline/openreq.py holds the
 // same rules on the host (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy   the window's span ranges into the tracker's own device buffer (complete when step()
-//          returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   insert every start record: absent -> OPEN; OPEN / COUNTED -> dup_start; marker -> start_after_sli,
 //   resolve every record the engine counts: OPEN -> removed; COUNTED -> removed + a correction
 //          (dup); absent -> a RESOLVED marker (a start that arrives after its SLI is dropped),
 //   sweep  the table: OPEN past its deadline -> counted (dl) and COUNTED; COUNTED past ttl and
 //          markers past reorder -> removed; the survivors move into the cleared other table, so
-//          no tombstone outlives a step and probe chains stay whole within one,
-//   publish the counters into the step's pinned host block (vector stores) and clear them.
+//          no tombstone outlives a step and probe chains stay whole within one.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,6 +25,7 @@
 
 #include "mislo_common.h"
 #include "openreq_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -52,44 +52,35 @@ struct StepArgs {
 void launch_insert(const Span* sp, int n, Table tb, StepArgs a, uint32_t* stats, hipStream_t st);
 void launch_resolve(const Span* sp, int n, Table tb, StepArgs a, uint32_t* dup, uint32_t* stats, hipStream_t st);
 void launch_sweep(Table cur, Table nxt, int64_t cap, StepArgs a, uint32_t* dl, uint32_t* stats, hipStream_t st);
-void launch_publish(uint32_t* counters, uint32_t* host, size_t words, hipStream_t st);
 
 }  // namespace openreq
 
 class OpenRequests {
  public:
   explicit OpenRequests(const openreq::Config& cfg);
-  ~OpenRequests();
-  OpenRequests(const OpenRequests&) = delete;
-  OpenRequests& operator=(const OpenRequests&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<openreq::Range>& spans, int64_t cut_ns, int64_t prev_cut_ns, int n_groups);
-  bool query(int64_t i);
-  void wait(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
+  void wait(int64_t i) { lane_.results(i); }
   // the step's result block (openreq::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone), ms
   std::pair<float, float> step_ms(int64_t i);
   // live entries sorted by trace hash (synchronous; tests)
   void entries(std::vector<uint64_t>& key, std::vector<int64_t>& t, std::vector<uint32_t>& grp,
                std::vector<uint32_t>& state);
-  void sync();
+  void sync() { lane_.sync(); }
   const openreq::Config& config() const { return cfg_; }
   const openreq::Layout& result_layout() const { return lay_; }
-  int64_t steps() const { return slots_.next(); }
+  int64_t steps() const { return lane_.steps(); }
 
  private:
   openreq::Config cfg_;
   openreq::Layout lay_;
-  openreq::SlotRing slots_;
-  hipStream_t st_ = nullptr;
-  openreq::Table tb_[2] = {};
+  StepLane lane_;
+  openreq::Table tb_[2] = {};  // the lane's arrays
   int cur_ = 0;
-  Span* spans_ = nullptr;
-  uint32_t* counters_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_end_;
 };
 
 }  // namespace mislo

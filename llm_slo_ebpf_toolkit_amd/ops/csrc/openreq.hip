@@ -11,13 +11,6 @@ namespace openreq {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 
 // Words other workgroups write in the same launch (keys, states) are read and written with
@@ -212,19 +205,6 @@ __global__ __launch_bounds__(kNT) void k_openreq_sweep(Table cur, Table nxt, int
       if (s_dl[i]) atomicAdd(&dl[i], s_dl[i]);
 }
 
-// the step's counters into its pinned host block, and cleared for the next step
-__global__ __launch_bounds__(kNT) void k_openreq_publish(uint4* __restrict__ counters, uint4* __restrict__ host,
-                                                         size_t n16) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = counters[i];
-    counters[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + kNT - 1) / kNT));
-}
-
 }  // namespace
 
 static_assert(kLiveCounted == kLiveOpen + 1 && kLiveResolved == kLiveOpen + 2 && kCounted == kOpen + 1 &&
@@ -233,94 +213,41 @@ static_assert(kLiveCounted == kLiveOpen + 1 && kLiveResolved == kLiveOpen + 2 &&
 
 void launch_insert(const Span* sp, int n, Table tb, StepArgs a, uint32_t* stats, hipStream_t st) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_openreq_insert, dim3(grid_for(n, 1024)), dim3(kNT), 0, st, sp, n, tb, a, stats);
+  hipLaunchKernelGGL(k_openreq_insert, dim3(grid_for(n, kNT, 1024)), dim3(kNT), 0, st, sp, n, tb, a, stats);
 }
 
 void launch_resolve(const Span* sp, int n, Table tb, StepArgs a, uint32_t* dup, uint32_t* stats, hipStream_t st) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_openreq_resolve, dim3(grid_for(n, 1024)), dim3(kNT), 0, st, sp, n, tb, a, dup, stats);
+  hipLaunchKernelGGL(k_openreq_resolve, dim3(grid_for(n, kNT, 1024)), dim3(kNT), 0, st, sp, n, tb, a, dup, stats);
 }
 
 void launch_sweep(Table cur, Table nxt, int64_t cap, StepArgs a, uint32_t* dl, uint32_t* stats, hipStream_t st) {
-  hipLaunchKernelGGL(k_openreq_sweep, dim3(grid_for(cap, 2048)), dim3(kNT), 0, st, cur, nxt, cap, a, dl, stats);
-}
-
-void launch_publish(uint32_t* counters, uint32_t* host, size_t words, hipStream_t st) {
-  const size_t n16 = words / 4;
-  hipLaunchKernelGGL(k_openreq_publish, dim3(grid_for((int64_t)n16, 64)), dim3(kNT), 0, st,
-                     reinterpret_cast<uint4*>(counters), reinterpret_cast<uint4*>(host), n16);
+  hipLaunchKernelGGL(k_openreq_sweep, dim3(grid_for(cap, kNT, 2048)), dim3(kNT), 0, st, cur, nxt, cap, a, dl, stats);
 }
 
 }  // namespace openreq
 
 using namespace openreq;
 
-OpenRequests::OpenRequests(const Config& cfg) : cfg_(cfg), lay_(layout(cfg.group_cap)), slots_(cfg.n_buffers) {
-  validate(cfg);
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+OpenRequests::OpenRequests(const Config& cfg)
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap)),
+      lane_("open-request", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 0) {
   const size_t cap = (size_t)cfg.cap;
   for (Table& tb : tb_) {
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&tb.key), cap * 8));
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&tb.t), cap * 8));
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&tb.grp), cap * 4));
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&tb.state), cap * 4));
-    HIPCHECK(hipMemsetAsync(tb.key, 0, cap * 8, st_));
-    HIPCHECK(hipMemsetAsync(tb.t, 0, cap * 8, st_));
-    HIPCHECK(hipMemsetAsync(tb.grp, 0, cap * 4, st_));
-    HIPCHECK(hipMemsetAsync(tb.state, 0, cap * 4, st_));
+    tb.key = lane_.zeroed<unsigned long long>(cap);
+    tb.t = lane_.zeroed<int64_t>(cap);
+    tb.grp = lane_.zeroed<uint32_t>(cap);
+    tb.state = lane_.zeroed<uint32_t>(cap);
   }
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&counters_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(counters_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    hipEvent_t e;
-    HIPCHECK(hipEventCreate(&e));
-    ev_begin_.push_back(e);
-    HIPCHECK(hipEventCreate(&e));
-    ev_copied_.push_back(e);
-    HIPCHECK(hipEventCreate(&e));
-    ev_end_.push_back(e);
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-OpenRequests::~OpenRequests() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  for (Table& tb : tb_) {
-    (void)hipFree(tb.key);
-    (void)hipFree(tb.t);
-    (void)hipFree(tb.grp);
-    (void)hipFree(tb.state);
-  }
-  (void)hipFree(spans_);
-  (void)hipFree(counters_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  lane_.ready();
 }
 
 int64_t OpenRequests::step(const std::vector<Range>& spans, int64_t cut_ns, int64_t prev_cut_ns, int n_groups) {
   check_step(cut_ns, prev_cut_ns, n_groups, cfg_.group_cap);
   const size_t n = plan_ranges(spans, cfg_.span_cap);
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
   StepArgs a;
   a.cut_ns = cut_ns;
   a.prev_cut_ns = prev_cut_ns;
@@ -330,46 +257,18 @@ int64_t OpenRequests::step(const std::vector<Range>& spans, int64_t cut_ns, int6
   a.slo_ms = (float)cfg_.slo_ms;
   a.n_groups = n_groups;
   a.mask = (uint64_t)cfg_.cap - 1;
-  uint32_t* c = counters_;
+  uint32_t* c = lane_.block();
   const Table cur = tb_[cur_], nxt = tb_[cur_ ^ 1];
-  launch_insert(spans_, (int)n, cur, a, c + lay_.stats, st_);
-  launch_resolve(spans_, (int)n, cur, a, c + lay_.dup, c + lay_.stats, st_);
-  launch_sweep(cur, nxt, cfg_.cap, a, c + lay_.dl, c + lay_.stats, st_);
-  launch_publish(c, host_[s], lay_.words, st_);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
+  launch_insert(lane_.spans(), (int)n, cur, a, c + lay_.stats, st);
+  launch_resolve(lane_.spans(), (int)n, cur, a, c + lay_.dup, c + lay_.stats, st);
+  launch_sweep(cur, nxt, cfg_.cap, a, c + lay_.dl, c + lay_.stats, st);
+  lane_.publish(s, 64);
   cur_ ^= 1;
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
   return idx;
 }
 
-bool OpenRequests::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slots_.slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-void OpenRequests::wait(int64_t i) { HIPCHECK(hipEventSynchronize(ev_end_[slots_.slot_of(i)])); }
-
-const uint32_t* OpenRequests::results(int64_t i) {
-  wait(i);
-  return host_[slots_.slot_of(i)];
-}
-
 std::pair<float, float> OpenRequests::step_ms(int64_t i) {
-  const int s = slots_.slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  return {all, kern};
-}
-
-void OpenRequests::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd)};
 }
 
 void OpenRequests::entries(std::vector<uint64_t>& key, std::vector<int64_t>& t, std::vector<uint32_t>& grp,

@@ -1,5 +1,5 @@
 // Host side of the open-request tracker (openreq.h) that needs no device: the configuration
-// and argument checks, the result block's layout and the bookkeeping of the result slots. Plain
+// and argument checks and the result block's layout (the result slots are steplane_host.h's). Plain
 // C++ (no HIP header), so it builds and runs on its own under the host sanitizers
 // (tests/native/openreq_host_check.cpp).
 #pragma once
@@ -13,12 +13,13 @@
 #include <utility>
 #include <vector>
 
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
+
 namespace mislo {
 namespace openreq {
 
 constexpr int kMaxProbes = 64;    // linear probes per lookup / insert
 constexpr int kLdsGroups = 1024;  // groups whose counters the kernels keep in LDS (decode.hip kSliLds)
-constexpr int kSpanBytes = 64;    // collector/records.py SPAN
 
 // entry states; kEmpty doubles as "being inserted by this launch", kDead marks an entry removed
 // in this step (the key stays until the step's end, so probe chains stay whole)
@@ -77,19 +78,9 @@ inline Layout layout(int group_cap) {
   return l;
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("open-request step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("open-request step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("open-request step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "open-request");
 }
 
 inline void check_step(int64_t cut_ns, int64_t prev_cut_ns, int n_groups, int group_cap) {
@@ -98,30 +89,7 @@ inline void check_step(int64_t cut_ns, int64_t prev_cut_ns, int n_groups, int gr
   if (n_groups < 0 || n_groups > group_cap) throw std::invalid_argument("open-request step: n_groups out of range");
 }
 
-// Result slots: step i writes slot i % n; its results stay readable until step i + n takes the slot.
-class SlotRing {
- public:
-  explicit SlotRing(int n) : idx_((size_t)(n > 0 ? n : 1), -1) {}
-  int size() const { return (int)idx_.size(); }
-  int64_t next() const { return next_; }
-  // the slot of the next step (its index is next()); the step it held before is forgotten
-  int begin() {
-    const int s = (int)(next_ % (int64_t)idx_.size());
-    idx_[(size_t)s] = next_++;
-    return s;
-  }
-  bool holds(int64_t i) const { return i >= 0 && i < next_ && idx_[(size_t)(i % (int64_t)idx_.size())] == i; }
-  int slot_of(int64_t i) const {
-    if (!holds(i))
-      throw std::out_of_range("open-request step " + std::to_string(i) + " is not held (only the last " +
-                              std::to_string(idx_.size()) + ")");
-    return (int)(i % (int64_t)idx_.size());
-  }
-
- private:
-  std::vector<int64_t> idx_;
-  int64_t next_ = 0;
-};
+using mislo::SlotRing;  // the result slots; "open-request" is its own default name
 
 }  // namespace openreq
 }  // namespace mislo

@@ -9,9 +9,9 @@
 // atomics only. The engine, its graphs and its streams are not touched. pipeline/podrank.py holds
 // the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   observe  one thread per record: insert or add into the window's table and the service totals;
 //            with `lds` every workgroup aggregates its pairs and totals in LDS first,
 //   rank     one thread per window-table slot: append the pair to the horizon's list step % H,
@@ -21,8 +21,8 @@
 //   rank     the same over the recent table,
 //   gather   one wave per service row, every row of group_cap: keys into rows by probing the
 //            tables, the totals of the window and of the horizon,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block
-//            and both tables.
+//   publish  this tracker's own kernel in place of the lane's: the result block into its pinned host block
+//            (vector stores); clears the block and both tables. Then the lane's finish().
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,8 +30,8 @@
 #include <vector>
 
 #include "mislo_common.h"
-#include "openreq_host.h"
 #include "podrank_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -57,42 +57,33 @@ struct PairList {
 class PodRankTracker {
  public:
   explicit PodRankTracker(const podrank::Config& cfg);
-  ~PodRankTracker();
-  PodRankTracker(const PodRankTracker&) = delete;
-  PodRankTracker& operator=(const PodRankTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<podrank::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (podrank::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the horizon's H pair lists, slot = step % windows, in no particular order (synchronous; tests)
   std::vector<podrank::PairList> resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const podrank::Config& config() const { return cfg_; }
   const podrank::Layout& result_layout() const { return lay_; }
 
  private:
-  int slot_of(int64_t i) const;
-  void alloc_pairs(podrank::Pairs& p, size_t n);
-  void free_pairs(podrank::Pairs& p);
+  podrank::Pairs zeroed_pairs(size_t n);
 
   podrank::Config cfg_;
   podrank::Layout lay_;
-  openreq::SlotRing slots_;
   uint32_t wslots_ = 0, rslots_ = 0;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
+  StepLane lane_;
+  // the lane's
   podrank::Pairs win_, rec_, lists_;     // [wslots] [rslots] [windows][pair_cap]
   uint32_t* ctrl_ = nullptr;             // [0] pairs claimed in the window's table, [1 + h] length of list h
   uint32_t* tot_ = nullptr;              // [2][group_cap] the step's n and b per service
   uint32_t* hist_ = nullptr;             // [windows][2][group_cap] the same of the horizon's steps
   unsigned long long* top_ = nullptr;    // [2][group_cap][k] the scopes' rank keys, 0 = empty
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

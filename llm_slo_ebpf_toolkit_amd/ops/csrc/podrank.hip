@@ -10,13 +10,6 @@ namespace podrank {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -332,172 +325,76 @@ __global__ __launch_bounds__(kNT) void k_podrank_publish(uint4* __restrict__ blo
     rec.key[i] = 0ull, rec.n[i] = 0u, rec.b[i] = 0u, rec.max[i] = 0u, rec.sum[i] = 0ull;
 }
 
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 }  // namespace podrank
 
 using namespace podrank;
 
-void PodRankTracker::alloc_pairs(Pairs& p, size_t n) {
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p.key), n * 8));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p.sum), n * 8));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p.n), n * 4));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p.b), n * 4));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&p.max), n * 4));
-  HIPCHECK(hipMemsetAsync(p.key, 0, n * 8, st_));
-  HIPCHECK(hipMemsetAsync(p.sum, 0, n * 8, st_));
-  HIPCHECK(hipMemsetAsync(p.n, 0, n * 4, st_));
-  HIPCHECK(hipMemsetAsync(p.b, 0, n * 4, st_));
-  HIPCHECK(hipMemsetAsync(p.max, 0, n * 4, st_));
+Pairs PodRankTracker::zeroed_pairs(size_t n) {
+  Pairs p;
+  p.key = lane_.zeroed<unsigned long long>(n);
+  p.sum = lane_.zeroed<unsigned long long>(n);
+  p.n = lane_.zeroed<uint32_t>(n);
+  p.b = lane_.zeroed<uint32_t>(n);
+  p.max = lane_.zeroed<uint32_t>(n);
+  return p;
 }
 
-void PodRankTracker::free_pairs(Pairs& p) {
-  (void)hipFree(p.key);
-  (void)hipFree(p.sum);
-  (void)hipFree(p.n);
-  (void)hipFree(p.b);
-  (void)hipFree(p.max);
-  p = Pairs();
-}
-
-PodRankTracker::PodRankTracker(const Config& cfg) : cfg_(cfg), slots_(cfg.n_buffers) {
-  validate(cfg);
-  lay_ = layout(cfg.group_cap, cfg.k);
+PodRankTracker::PodRankTracker(const Config& cfg)
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap, cfg.k)),
+      lane_("pod breakdown", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
   wslots_ = window_slots(cfg), rslots_ = recent_slots(cfg);
   const size_t G = (size_t)cfg.group_cap, K = (size_t)cfg.k, H = (size_t)cfg.windows;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  alloc_pairs(win_, wslots_);
-  alloc_pairs(rec_, rslots_);
-  alloc_pairs(lists_, H * (size_t)cfg.pair_cap);
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&ctrl_), (1 + H) * 4));
-  HIPCHECK(hipMemsetAsync(ctrl_, 0, (1 + H) * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&tot_), 2 * G * 4));
-  HIPCHECK(hipMemsetAsync(tot_, 0, 2 * G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&hist_), H * 2 * G * 4));
-  HIPCHECK(hipMemsetAsync(hist_, 0, H * 2 * G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&top_), 2 * G * K * 8));
-  HIPCHECK(hipMemsetAsync(top_, 0, 2 * G * K * 8, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    for (auto* v : {&ev_begin_, &ev_copied_, &ev_observed_, &ev_end_}) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      v->push_back(e);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-PodRankTracker::~PodRankTracker() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(spans_);
-  free_pairs(win_);
-  free_pairs(rec_);
-  free_pairs(lists_);
-  (void)hipFree(ctrl_);
-  (void)hipFree(tot_);
-  (void)hipFree(hist_);
-  (void)hipFree(top_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_observed_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  win_ = zeroed_pairs(wslots_);
+  rec_ = zeroed_pairs(rslots_);
+  lists_ = zeroed_pairs(H * (size_t)cfg.pair_cap);
+  ctrl_ = lane_.zeroed<uint32_t>(1 + H);
+  tot_ = lane_.zeroed<uint32_t>(2 * G);
+  hist_ = lane_.zeroed<uint32_t>(H * 2 * G);
+  top_ = lane_.zeroed<unsigned long long>(2 * G * K);
+  lane_.ready();
 }
 
 int64_t PodRankTracker::step(const std::vector<Range>& spans, int n_groups) {
   check_step(n_groups, cfg_.group_cap);
   const size_t n = plan_ranges(spans, cfg_.span_cap);
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
   const int G = cfg_.group_cap, K = cfg_.k, H = cfg_.windows, cur = (int)(idx % (int64_t)H);
   const uint32_t cap = (uint32_t)cfg_.pair_cap, wmask = wslots_ - 1u, rmask = rslots_ - 1u;
-  uint32_t* stats = block_ + lay_.stats;
+  uint32_t* stats = blk + lay_.stats;
   u64* wtop = top_;
   u64* rtop = top_ + (size_t)G * K;
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
   // an empty step still launches: block 0 resets the list this step refills
   const dim3 block(kNT), og(grid_for((int64_t)n, kNT, 1024));
   const float slo = (float)cfg_.slo_ms;
   if (cfg_.lds)
-    hipLaunchKernelGGL(k_podrank_observe<true>, og, block, 0, st_, spans_, (int)n, n_groups, slo, win_, wmask, cap, ctrl_,
-                       cur, tot_, G, stats);
+    hipLaunchKernelGGL(k_podrank_observe<true>, og, block, 0, st, lane_.spans(), (int)n, n_groups, slo, win_, wmask, cap,
+                       ctrl_, cur, tot_, G, stats);
   else
-    hipLaunchKernelGGL(k_podrank_observe<false>, og, block, 0, st_, spans_, (int)n, n_groups, slo, win_, wmask, cap, ctrl_,
-                       cur, tot_, G, stats);
-  HIPCHECK(hipEventRecord(ev_observed_[s], st_));
-  hipLaunchKernelGGL(k_podrank_rank, dim3(grid_for(wslots_, kNT, 1024)), block, 0, st_, win_, wslots_, wtop, K,
-                     block_ + lay_.pods[0], block_ + lay_.pods_b[0], lists_, ctrl_, cur, cap, G, stats);
-  hipLaunchKernelGGL(k_podrank_roll, dim3(grid_for((int64_t)H * cap, kNT, 1024)), block, 0, st_, lists_, ctrl_, H, cap,
-                     rec_, rmask);
-  hipLaunchKernelGGL(k_podrank_rank, dim3(grid_for(rslots_, kNT, 1024)), block, 0, st_, rec_, rslots_, rtop, K,
-                     block_ + lay_.pods[1], block_ + lay_.pods_b[1], Pairs(), ctrl_, cur, cap, G, stats);
-  hipLaunchKernelGGL(k_podrank_gather, dim3(grid_for(G, kRowsPerBlock, 1 << 20)), block, 0, st_, win_, wmask, rec_, rmask,
-                     top_, tot_, hist_, block_, lay_, G, K, H, cur);
+    hipLaunchKernelGGL(k_podrank_observe<false>, og, block, 0, st, lane_.spans(), (int)n, n_groups, slo, win_, wmask, cap,
+                       ctrl_, cur, tot_, G, stats);
+  lane_.mark(s, StepLane::kObserved);
+  hipLaunchKernelGGL(k_podrank_rank, dim3(grid_for(wslots_, kNT, 1024)), block, 0, st, win_, wslots_, wtop, K,
+                     blk + lay_.pods[0], blk + lay_.pods_b[0], lists_, ctrl_, cur, cap, G, stats);
+  hipLaunchKernelGGL(k_podrank_roll, dim3(grid_for((int64_t)H * cap, kNT, 1024)), block, 0, st, lists_, ctrl_, H, cap, rec_,
+                     rmask);
+  hipLaunchKernelGGL(k_podrank_rank, dim3(grid_for(rslots_, kNT, 1024)), block, 0, st, rec_, rslots_, rtop, K,
+                     blk + lay_.pods[1], blk + lay_.pods_b[1], Pairs(), ctrl_, cur, cap, G, stats);
+  hipLaunchKernelGGL(k_podrank_gather, dim3(grid_for(G, kRowsPerBlock, 1 << 20)), block, 0, st, win_, wmask, rec_, rmask,
+                     top_, tot_, hist_, blk, lay_, G, K, H, cur);
   const size_t n16 = lay_.words / 4;
-  hipLaunchKernelGGL(k_podrank_publish, dim3(grid_for((int64_t)std::max<size_t>(n16, rslots_), kNT, 1024)), block, 0, st_,
-                     reinterpret_cast<uint4*>(block_), reinterpret_cast<uint4*>(host_[s]), n16, win_, wslots_, rec_,
-                     rslots_);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  hipLaunchKernelGGL(k_podrank_publish, dim3(grid_for((int64_t)std::max<size_t>(n16, rslots_), kNT, 1024)), block, 0, st,
+                     reinterpret_cast<uint4*>(blk), reinterpret_cast<uint4*>(lane_.host(s)), n16, win_, wslots_, rec_, rslots_);
+  lane_.finish(s);
   return idx;
 }
 
-int PodRankTracker::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("pod breakdown step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool PodRankTracker::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* PodRankTracker::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::vector<float> PodRankTracker::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f, obs = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&obs, ev_copied_[s], ev_observed_[s]));
-  return {all, kern, obs};
-}
-
-void PodRankTracker::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd),
+          lane_.ms(i, StepLane::kCopied, StepLane::kObserved)};
 }
 
 std::vector<PairList> PodRankTracker::resident() {

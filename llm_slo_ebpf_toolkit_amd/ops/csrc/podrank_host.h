@@ -13,6 +13,8 @@
 #include <utility>
 #include <vector>
 
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
+
 #if defined(__HIPCC__)
 #define MISLO_PR_HD __host__ __device__
 #else
@@ -30,7 +32,6 @@ constexpr int kCountBits = 22;         // requests and breaches of one pair over
 constexpr uint32_t kCountLimit = 1u << kCountBits;
 constexpr int kMaxPairCap = 1 << 20;
 constexpr float kMaxMs = 2097152.0f;   // 2^21: the sum's clamp (the TTFT sketch's)
-constexpr int kSpanBytes = 64;         // collector/records.py SPAN
 constexpr int kRowBytes = 32;
 constexpr int kRowWords = kRowBytes / 4;
 constexpr int kLdsSlots = 256;         // the observe kernel's per-workgroup table (28 B a slot, 7 KB)
@@ -156,19 +157,9 @@ inline void validate(const Config& c) {
   if (device_bytes(c) > (uint64_t(1) << 31)) throw std::invalid_argument("pod breakdown: the tables need more than 2 GiB");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("pod breakdown step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("pod breakdown step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("pod breakdown step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "pod breakdown");
 }
 
 inline void check_step(int n_groups, int group_cap) {

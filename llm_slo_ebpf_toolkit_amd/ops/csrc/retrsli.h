@@ -11,17 +11,16 @@
 // the steps it has held. The engine, its graphs and its streams are not touched. pipeline/retrsli.py holds
 // the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window, between the
+// lane's copy and its publish:
 //   observe  one thread per record: up to six adds per observed record (its retrieval bucket, its model
 //            bucket, its cell, the two 64-bit sums, the SLI count). With `lds` every workgroup aggregates
 //            in an LDS table first and sends each key once. Not launched for an empty step,
 //   roll     two waves per service row, one per histogram, every row of group_cap: the window of W steps
 //            ago leaves the rolling row, this one enters and takes its place, the step's row is cleared;
 //            the four ranks of the window's and the rolling row by a wave scan; the wave of the retrieval
-//            histogram rolls the counters and the sums alike and its lane 0 decides the verdict,
-//   publish  the step's result block into its pinned host block (vector stores); clears the block.
+//            histogram rolls the counters and the sums alike and its lane 0 decides the verdict.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -29,8 +28,8 @@
 #include <vector>
 
 #include "mislo_common.h"
-#include "openreq_host.h"
 #include "retrsli_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -52,27 +51,23 @@ struct Resident {
 class RetrievalSliTracker {
  public:
   explicit RetrievalSliTracker(const retrsli::Config& cfg);
-  ~RetrievalSliTracker();
-  RetrievalSliTracker(const RetrievalSliTracker&) = delete;
-  RetrievalSliTracker& operator=(const RetrievalSliTracker&) = delete;
 
   // One window; returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<retrsli::Range>& spans, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (retrsli::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the rolling rows, counters, sums, verdicts and the ring position (synchronous; tests)
   retrsli::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   const retrsli::Config& config() const { return cfg_; }
   const retrsli::Layout& result_layout() const { return lay_; }
   uint32_t slo_units() const { return slo_u_; }
   uint32_t budget_units() const { return budget_u_; }
 
  private:
-  int slot_of(int64_t i) const;
   // row `which` of the state: [0, W) the horizon's windows, W the rolling row, W + 1 this step's
   uint32_t* hist_r(size_t which) const { return hist_r_ + which * (size_t)cfg_.group_cap * retrsli::kK; }
   uint32_t* hist_m(size_t which) const { return hist_m_ + which * (size_t)cfg_.group_cap * retrsli::kK; }
@@ -81,18 +76,13 @@ class RetrievalSliTracker {
 
   retrsli::Config cfg_;
   retrsli::Layout lay_;
-  openreq::SlotRing slots_;
   uint32_t slo_u_ = 0, budget_u_ = 0;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
-  uint32_t* hist_r_ = nullptr;
+  StepLane lane_;
+  uint32_t* hist_r_ = nullptr;  // the lane's, like the four below
   uint32_t* hist_m_ = nullptr;
   uint32_t* cells_ = nullptr;
   unsigned long long* sum_ = nullptr;
   uint32_t* verdict_ = nullptr;  // [2][group_cap]: state, age
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

@@ -23,6 +23,7 @@
 #include "decodesli_host.h"  // bucket_of, lower, representative, kK, kPerLane, kRowLanes: the histograms' rule
 #include "errsli_host.h"     // budget_ppm: the error budget of an SLO target, in millionths
 #include "slisketch_host.h"  // rank_of, quantile_permille, kQuantiles, kEmpty
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace retrsli {
@@ -43,7 +44,6 @@ constexpr int kCellStride = 8;                   // a service's counters: the si
 constexpr int kSliWord = 6;
 constexpr int kStates = 5;                       // unknown ok retrieval_bound model_bound mixed
 constexpr uint64_t kPpm = 1000000ull;
-constexpr int kSpanBytes = 64;                   // collector/records.py SPAN
 constexpr int kLdsBits = 10;
 constexpr int kLdsSlots = 1 << kLdsBits;         // the observe kernel's per-workgroup table (16 B a slot, 16 KB)
 constexpr int kLdsProbes = onset::kLdsProbes;    // LDS probes before an add goes to global memory itself
@@ -214,19 +214,9 @@ inline void validate(const Config& c) {
     throw std::invalid_argument("retrieval sli: a result block needs more than 2 GiB");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("retrieval sli step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("retrieval sli step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("retrieval sli step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "retrieval sli");
 }
 
 inline void check_step(int n_groups, int group_cap) {

@@ -13,9 +13,9 @@
 // graphs and its streams are not touched; the load tracker's ring is not shared.
 // pipeline/satcurve.py holds the same rules in numpy (the oracle, and what the CPU engine uses).
 //
-// Native, no PyTorch, its own stream, plain launches (no graphs). One step per window with a timed cut:
-//   copy     the window's span ranges into the tracker's own device buffer (complete when step()
-//            returns: the rings' release contract stays the engine's),
+// Native, no PyTorch, plain launches (no graphs) on a step lane of its own (steplane.h: the stream, the
+// copy of the window's span ranges, the result slots, the publish). One step per window with a timed cut, between the
+// lane's copy and its publish:
 //   clear    the generations the step's evicted epochs invalidate (the host keeps their epochs),
 //   fold     one wave per row: a wave scan of the evicted bins' starts - ends from carry gives every
 //            evicted bin its level; bins with whole history add their sli into the row's generation,
@@ -25,8 +25,8 @@
 //   scan     one wave per service row, every row of group_cap: the load tracker's scan, the settled
 //            bins' sli into a wave-private LDS histogram by level, the recent busy time; then three
 //            levels a lane: the live generations added, the suffix scan of the scores, the arg-max,
-//            the suffix counts at the knee; lane 0 decides the state and stores the row,
-//   publish  the step's result block into its pinned host block (vector stores); clears the statistics.
+//            the suffix counts at the knee; lane 0 decides the state and stores the row.
+// The lane's publish clears the statistics alone: the rows and the curve are rewritten whole by every scan.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,8 +34,8 @@
 #include <vector>
 
 #include "mislo_common.h"
-#include "openreq_host.h"
 #include "satcurve_host.h"
+#include "steplane.h"
 
 namespace mislo {
 
@@ -56,45 +56,36 @@ struct Resident {
 class SaturationTracker {
  public:
   explicit SaturationTracker(const satcurve::Config& cfg);
-  ~SaturationTracker();
-  SaturationTracker(const SaturationTracker&) = delete;
-  SaturationTracker& operator=(const SaturationTracker&) = delete;
 
   // One window cut at cut_ns (> 0); returns the step's index. The ranges are read before it returns.
   int64_t step(const std::vector<satcurve::Range>& spans, int64_t cut_ns, int n_groups);
-  bool query(int64_t i);
+  bool query(int64_t i) { return lane_.query(i); }
   // the step's result block (satcurve::layout), valid until n_buffers later steps; waits for it
-  const uint32_t* results(int64_t i);
+  const uint32_t* results(int64_t i) { return lane_.results(i); }
   // device time of the step: (copy + kernels, kernels alone, the observe kernel alone), ms
   std::vector<float> step_ms(int64_t i);
   // the ring, the generations and what goes with them (synchronous; tests)
   satcurve::Resident resident();
-  void sync();
+  void sync() { lane_.sync(); }
   int64_t q_hi() const { return q_hi_; }
   const satcurve::Config& config() const { return cfg_; }
   const satcurve::Layout& result_layout() const { return lay_; }
 
  private:
-  int slot_of(int64_t i) const;
-
   satcurve::Config cfg_;
   satcurve::Layout lay_;
-  openreq::SlotRing slots_;
   satcurve::RingPopulation ring_pop_;
   satcurve::CurvePopulation curve_pop_;
   satcurve::Generations gens_;
   int64_t q_hi_ = satcurve::kNoBin, q_first_ = satcurve::kNoBin;
-  hipStream_t st_ = nullptr;
-  Span* spans_ = nullptr;
+  StepLane lane_;
+  // the lane's
   unsigned long long* counts_ = nullptr;  // [group_cap][bins]
   unsigned long long* idle_ = nullptr;    // [group_cap][bins]
   unsigned long long* sli_ = nullptr;     // [group_cap][bins]
   unsigned long long* gen_ = nullptr;     // [2][group_cap][kK][2]
   int32_t* carry_ = nullptr;              // [group_cap]
   uint32_t* age_ = nullptr;               // [group_cap]
-  uint32_t* block_ = nullptr;
-  std::vector<uint32_t*> host_;
-  std::vector<hipEvent_t> ev_begin_, ev_copied_, ev_advanced_, ev_observed_, ev_end_;
 };
 
 }  // namespace mislo

@@ -10,13 +10,6 @@ namespace satcurve {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -322,20 +315,6 @@ __global__ __launch_bounds__(kNT) void k_sat_scan(const u64* __restrict__ counts
   }
 }
 
-// the step's result block into its pinned host block; the statistics (from clear_from on) cleared for
-// the next step -- the rows and the curve are rewritten whole by every scan
-__global__ __launch_bounds__(kNT) void k_sat_publish(uint4* __restrict__ block, uint4* __restrict__ host, size_t n16,
-                                                     size_t clear_from) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = block[i];
-    if (i >= clear_from) block[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 }  // namespace satcurve
 
@@ -343,57 +322,18 @@ using namespace satcurve;
 
 SaturationTracker::SaturationTracker(const Config& cfg)
     : cfg_(cfg),
-      slots_(cfg.n_buffers),
+      lay_(layout(cfg.group_cap)),
       ring_pop_((uint32_t)cfg.bins, cfg.ring_records_max),
-      curve_pop_(cfg.epoch_bins, cfg.curve_records_max) {
-  validate(cfg);
-  lay_ = layout(cfg.group_cap);
+      curve_pop_(cfg.epoch_bins, cfg.curve_records_max),
+      lane_("saturation curve", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 2) {
   const size_t cells = (size_t)cfg.group_cap * (size_t)cfg.bins, G = (size_t)cfg.group_cap;
-  const size_t gen_bytes = G * 2 * kK * 16;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  for (u64** p : {&counts_, &idle_, &sli_}) {
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(p), cells * 8));
-    HIPCHECK(hipMemsetAsync(*p, 0, cells * 8, st_));
-  }
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&gen_), gen_bytes));
-  HIPCHECK(hipMemsetAsync(gen_, 0, gen_bytes, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&carry_), G * 4));
-  HIPCHECK(hipMemsetAsync(carry_, 0, G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&age_), G * 4));
-  HIPCHECK(hipMemsetAsync(age_, 0, G * 4, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    for (auto* v : {&ev_begin_, &ev_copied_, &ev_advanced_, &ev_observed_, &ev_end_}) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      v->push_back(e);
-    }
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-SaturationTracker::~SaturationTracker() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(spans_);
-  (void)hipFree(counts_);
-  (void)hipFree(idle_);
-  (void)hipFree(sli_);
-  (void)hipFree(gen_);
-  (void)hipFree(carry_);
-  (void)hipFree(age_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_advanced_, &ev_observed_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  counts_ = lane_.zeroed<u64>(cells);
+  idle_ = lane_.zeroed<u64>(cells);
+  sli_ = lane_.zeroed<u64>(cells);
+  gen_ = lane_.zeroed<u64>(G * 2 * kK * 2);
+  carry_ = lane_.zeroed<int32_t>(G);
+  age_ = lane_.zeroed<uint32_t>(G);
+  lane_.ready();
 }
 
 int64_t SaturationTracker::step(const std::vector<Range>& spans, int64_t cut_ns, int n_groups) {
@@ -410,89 +350,43 @@ int64_t SaturationTracker::step(const std::vector<Range>& spans, int64_t cut_ns,
   const uint32_t clear = gens_.begin(fold, cfg_.epoch_bins);
   q_hi_ = q_hi;
   if (prev == kNoBin || q_hi - prev >= (int64_t)bins) q_first_ = q_hi;
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
   const int G = cfg_.group_cap;
-  uint32_t* stats = block_ + lay_.stats;
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
+  uint32_t* stats = blk + lay_.stats;
   const size_t gen_words = (size_t)G * kK * 2;  // one generation, every row
   for (int p = 0; p < 2; ++p)
-    if (clear >> p & 1u) HIPCHECK(hipMemsetAsync(gen_ + (size_t)p * gen_words, 0, gen_words * 8, st_));
+    if (clear >> p & 1u) HIPCHECK(hipMemsetAsync(gen_ + (size_t)p * gen_words, 0, gen_words * 8, st));
   const dim3 block(kNT), rows(grid_for(G, kRowsPerBlock, 1 << 20));
   if (fold.count)
-    hipLaunchKernelGGL(k_sat_fold, rows, block, 0, st_, counts_, idle_, sli_, gen_, carry_, G, bins, fold.first, fold.count,
+    hipLaunchKernelGGL(k_sat_fold, rows, block, 0, st, counts_, idle_, sli_, gen_, carry_, G, bins, fold.first, fold.count,
                        fold.lo, cfg_.bin_us, cfg_.epoch_bins);
-  HIPCHECK(hipEventRecord(ev_advanced_[s], st_));
+  lane_.mark(s, StepLane::kAdvanced);
   if (n) {
     const dim3 og(grid_for((int64_t)n, kNT, 1024));
     const float slo = (float)cfg_.slo_ms;
     if (cfg_.lds)
-      hipLaunchKernelGGL(k_sat_observe<true>, og, block, 0, st_, spans_, (int)n, n_groups, cfg_.bin_us, q_hi, bins, slo,
+      hipLaunchKernelGGL(k_sat_observe<true>, og, block, 0, st, lane_.spans(), (int)n, n_groups, cfg_.bin_us, q_hi, bins, slo,
                          counts_, idle_, sli_, carry_, stats);
     else
-      hipLaunchKernelGGL(k_sat_observe<false>, og, block, 0, st_, spans_, (int)n, n_groups, cfg_.bin_us, q_hi, bins, slo,
-                         counts_, idle_, sli_, carry_, stats);
+      hipLaunchKernelGGL(k_sat_observe<false>, og, block, 0, st, lane_.spans(), (int)n, n_groups, cfg_.bin_us, q_hi, bins,
+                         slo, counts_, idle_, sli_, carry_, stats);
   }
-  HIPCHECK(hipEventRecord(ev_observed_[s], st_));
+  lane_.mark(s, StepLane::kObserved);
   ScanParams P;
   P.q_hi = q_hi, P.q_first = q_first_, P.bin_us = cfg_.bin_us, P.epoch_bins = cfg_.epoch_bins;
   P.budget_ppm = cfg_.budget_ppm, P.min_requests = cfg_.min_requests, P.bins = bins;
   P.live = gens_.live(epoch_now(onset::oldest_bin(q_hi, bins), cfg_.epoch_bins));
   P.settle = cfg_.settle_bins, P.recent = cfg_.recent_bins, P.group_cap = G;
-  hipLaunchKernelGGL(k_sat_scan, rows, block, 0, st_, counts_, idle_, sli_, gen_, carry_, age_, P, block_, lay_.rows,
-                     lay_.curve);
-  const size_t n16 = lay_.words / 4;
-  hipLaunchKernelGGL(k_sat_publish, dim3(grid_for((int64_t)n16, kNT, 1024)), block, 0, st_,
-                     reinterpret_cast<uint4*>(block_), reinterpret_cast<uint4*>(host_[s]), n16, lay_.stats / 4);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  hipLaunchKernelGGL(k_sat_scan, rows, block, 0, st, counts_, idle_, sli_, gen_, carry_, age_, P, blk, lay_.rows, lay_.curve);
+  lane_.publish(s, 1024, lay_.stats / 4);
   return idx;
 }
 
-int SaturationTracker::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("saturation curve step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool SaturationTracker::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* SaturationTracker::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::vector<float> SaturationTracker::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f, obs = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&obs, ev_advanced_[s], ev_observed_[s]));
-  return {all, kern, obs};
-}
-
-void SaturationTracker::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd),
+          lane_.ms(i, StepLane::kAdvanced, StepLane::kObserved)};
 }
 
 Resident SaturationTracker::resident() {

@@ -39,6 +39,7 @@
 #include "errsli_host.h"
 #include "loadsli_host.h"
 #include "onset_host.h"
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
 
 namespace mislo {
 namespace satcurve {
@@ -62,7 +63,6 @@ constexpr int64_t kMillion = 1000000ll;
 constexpr int64_t kMaxEpochBins = 2147483647ll;
 constexpr int64_t kMaxMinRequests = 2147483647ll;
 constexpr int64_t kMaxCurveRecords = int64_t(1) << 40;
-constexpr int kSpanBytes = 64;  // collector/records.py SPAN
 constexpr int kRowBytes = 64;
 constexpr int kRowWords = kRowBytes / 4;
 constexpr int kCurveWords = kK * 4;  // a row's merged curve: kK x (u64 n, u64 b)
@@ -264,19 +264,9 @@ inline void validate(const Config& c) {
     throw std::invalid_argument("saturation curve: curve_records_max must be in [1, 2^40]");
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("saturation curve step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("saturation curve step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n) throw std::invalid_argument("saturation curve step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "saturation curve");
 }
 
 inline void check_step(int64_t cut_ns, int n_groups, int group_cap) {

@@ -10,13 +10,6 @@ namespace slisketch {
 
 namespace {
 
-#define HIPCHECK(x)                                                                                  \
-  do {                                                                                               \
-    hipError_t _e = (x);                                                                             \
-    if (_e != hipSuccess) throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + \
-                                                   " at " #x);                                       \
-  } while (0)
-
 constexpr int kNT = 256;
 constexpr int kWave = 64;
 constexpr int kRowsPerBlock = kNT / kWave;
@@ -135,19 +128,6 @@ __global__ __launch_bounds__(kNT) void k_sketch_roll(uint32_t* __restrict__ cur,
   }
 }
 
-// the step's result block into its pinned host block, and cleared for the next step
-__global__ __launch_bounds__(kNT) void k_sketch_publish(uint4* __restrict__ block, uint4* __restrict__ host,
-                                                        size_t n16) {
-  for (size_t i = blockIdx.x * (size_t)kNT + threadIdx.x; i < n16; i += (size_t)gridDim.x * kNT) {
-    host[i] = block[i];
-    block[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-}
-
-int grid_for(int64_t n, int per_block, int max_blocks) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(max_blocks, (n + per_block - 1) / per_block));
-}
-
 }  // namespace
 
 void launch_observe(const Span* sp, int n, int n_groups, uint32_t* cur, uint32_t* le, unsigned long long* sum,
@@ -163,116 +143,36 @@ void launch_roll(uint32_t* cur, uint32_t* slot, uint32_t* roll, unsigned long lo
                      roll, sum, block, lay, group_cap);
 }
 
-void launch_publish(uint32_t* block, uint32_t* host, size_t words, hipStream_t st) {
-  const size_t n16 = words / 4;
-  hipLaunchKernelGGL(k_sketch_publish, dim3(grid_for((int64_t)n16, kNT, 64)), dim3(kNT), 0, st,
-                     reinterpret_cast<uint4*>(block), reinterpret_cast<uint4*>(host), n16);
-}
-
 }  // namespace slisketch
 
 using namespace slisketch;
 
-SliSketch::SliSketch(const Config& cfg) : cfg_(cfg), lay_(layout(cfg.group_cap)), slots_(cfg.n_buffers) {
-  validate(cfg);
+SliSketch::SliSketch(const Config& cfg)
+    : cfg_(cfg),
+      lay_(layout(cfg.group_cap)),
+      lane_("ttft sketch", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 0) {
   row_words_ = (size_t)cfg.group_cap * kRowStride;
-  HIPCHECK(hipSetDevice(cfg.device));
-  HIPCHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&hist_), device_bytes(cfg)));
-  HIPCHECK(hipMemsetAsync(hist_, 0, device_bytes(cfg), st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&spans_), (size_t)cfg.span_cap * sizeof(Span)));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&sum_), (size_t)cfg.group_cap * 8));
-  HIPCHECK(hipMemsetAsync(sum_, 0, (size_t)cfg.group_cap * 8, st_));
-  HIPCHECK(hipMalloc(reinterpret_cast<void**>(&block_), lay_.words * 4));
-  HIPCHECK(hipMemsetAsync(block_, 0, lay_.words * 4, st_));
-  for (int i = 0; i < cfg.n_buffers; ++i) {
-    void* h = nullptr;
-    HIPCHECK(hipHostMalloc(&h, lay_.words * 4, hipHostMallocCoherent | hipHostMallocMapped));
-    std::fill_n(static_cast<uint32_t*>(h), lay_.words, 0u);
-    host_.push_back(static_cast<uint32_t*>(h));
-    hipEvent_t e;
-    HIPCHECK(hipEventCreate(&e));
-    ev_begin_.push_back(e);
-    HIPCHECK(hipEventCreate(&e));
-    ev_copied_.push_back(e);
-    HIPCHECK(hipEventCreate(&e));
-    ev_end_.push_back(e);
-  }
-  HIPCHECK(hipStreamSynchronize(st_));
-}
-
-SliSketch::~SliSketch() {
-  (void)hipSetDevice(cfg_.device);
-  if (st_) (void)hipStreamSynchronize(st_);
-  (void)hipFree(hist_);
-  (void)hipFree(spans_);
-  (void)hipFree(sum_);
-  (void)hipFree(block_);
-  for (uint32_t* h : host_) (void)hipHostFree(h);
-  for (auto* v : {&ev_begin_, &ev_copied_, &ev_end_})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (st_) (void)hipStreamDestroy(st_);
+  hist_ = lane_.zeroed<uint32_t>(device_bytes(cfg) / 4);
+  sum_ = lane_.zeroed<unsigned long long>((size_t)cfg.group_cap);
+  lane_.ready();
 }
 
 int64_t SliSketch::step(const std::vector<Range>& spans, int n_groups) {
   check_step(n_groups, cfg_.group_cap);
   const size_t n = plan_ranges(spans, cfg_.span_cap);
-  HIPCHECK(hipSetDevice(cfg_.device));
-  const int64_t idx = slots_.next();
-  const int s = slots_.begin();
-  HIPCHECK(hipEventRecord(ev_begin_[s], st_));
-  size_t off = 0;
-  for (const Range& r : spans) {
-    if (!r.second) continue;
-    HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(spans_) + off, reinterpret_cast<const void*>(r.first), r.second,
-                            hipMemcpyHostToDevice, st_));
-    off += r.second;
-  }
-  HIPCHECK(hipEventRecord(ev_copied_[s], st_));
+  const auto [idx, s] = lane_.begin(spans);
+  const hipStream_t st = lane_.stream();
+  uint32_t* const blk = lane_.block();
   const size_t W = (size_t)cfg_.windows;
   uint32_t* cur = rows(W + 1);
-  launch_observe(spans_, (int)n, n_groups, cur, block_ + lay_.le, sum_, block_ + lay_.stats, st_);
-  launch_roll(cur, rows((size_t)(idx % (int64_t)W)), rows(W), sum_, block_, lay_, cfg_.group_cap, st_);
-  launch_publish(block_, host_[s], lay_.words, st_);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipEventRecord(ev_end_[s], st_));
-  // the ranges belong to the caller again once this returns
-  HIPCHECK(hipEventSynchronize(ev_copied_[s]));
+  launch_observe(lane_.spans(), (int)n, n_groups, cur, blk + lay_.le, sum_, blk + lay_.stats, st);
+  launch_roll(cur, rows((size_t)(idx % (int64_t)W)), rows(W), sum_, blk, lay_, cfg_.group_cap, st);
+  lane_.publish(s, 64);
   return idx;
 }
 
-int SliSketch::slot_of(int64_t i) const {
-  if (!slots_.holds(i))
-    throw std::out_of_range("ttft sketch step " + std::to_string(i) + " is not held (only the last " +
-                            std::to_string(slots_.size()) + ")");
-  return slots_.slot_of(i);
-}
-
-bool SliSketch::query(int64_t i) {
-  const hipError_t e = hipEventQuery(ev_end_[slot_of(i)]);
-  if (e == hipSuccess) return true;
-  if (e != hipErrorNotReady) HIPCHECK(e);
-  return false;
-}
-
-const uint32_t* SliSketch::results(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  return host_[s];
-}
-
 std::pair<float, float> SliSketch::step_ms(int64_t i) {
-  const int s = slot_of(i);
-  HIPCHECK(hipEventSynchronize(ev_end_[s]));
-  float all = 0.f, kern = 0.f;
-  HIPCHECK(hipEventElapsedTime(&all, ev_begin_[s], ev_end_[s]));
-  HIPCHECK(hipEventElapsedTime(&kern, ev_copied_[s], ev_end_[s]));
-  return {all, kern};
-}
-
-void SliSketch::sync() {
-  HIPCHECK(hipSetDevice(cfg_.device));
-  HIPCHECK(hipStreamSynchronize(st_));
+  return {lane_.ms(i, StepLane::kBegin, StepLane::kEnd), lane_.ms(i, StepLane::kCopied, StepLane::kEnd)};
 }
 
 std::vector<uint32_t> SliSketch::read_rows(const uint32_t* dev) {
@@ -289,7 +189,7 @@ std::vector<uint32_t> SliSketch::read_rows(const uint32_t* dev) {
 std::vector<uint32_t> SliSketch::rolling() { return read_rows(rows((size_t)cfg_.windows)); }
 
 std::vector<uint32_t> SliSketch::window_hist() {
-  const int64_t n = slots_.next();
+  const int64_t n = lane_.steps();
   return read_rows(n ? rows((size_t)((n - 1) % (int64_t)cfg_.windows)) : nullptr);
 }
 

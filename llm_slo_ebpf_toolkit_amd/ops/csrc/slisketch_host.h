@@ -13,6 +13,8 @@
 #include <utility>
 #include <vector>
 
+#include "steplane_host.h"  // Range, plan_ranges, kSpanBytes
+
 #if defined(__HIPCC__)
 #define MISLO_SK_HD __host__ __device__
 #else
@@ -35,7 +37,6 @@ constexpr int kEdges = 7;                   // REF's llm_slo_ttft_ms boundaries
 constexpr int kLe = kEdges + 1;             // + the +Inf slot
 constexpr int kQuantiles = 4;
 constexpr uint32_t kEmpty = 0xffffffffu;    // quantile of a group without a record
-constexpr int kSpanBytes = 64;              // collector/records.py SPAN
 
 MISLO_SK_HD inline float le_edge(int j) {
   return j == 0 ? 50.f : j == 1 ? 100.f : j == 2 ? 200.f : j == 3 ? 400.f : j == 4 ? 800.f : j == 5 ? 1200.f : 2000.f;
@@ -140,20 +141,9 @@ inline Layout layout(int group_cap) {
   return l;
 }
 
-using Range = std::pair<uintptr_t, size_t>;  // (host address, bytes)
-
-// the span records in `ranges`; throws when they are not whole records or exceed span_cap
+using mislo::Range;
 inline size_t plan_ranges(const std::vector<Range>& ranges, int span_cap) {
-  size_t n = 0;
-  for (const Range& r : ranges) {
-    if (r.second == 0) continue;
-    if (r.first == 0) throw std::invalid_argument("ttft sketch step: null range");
-    if (r.second % kSpanBytes) throw std::invalid_argument("ttft sketch step: a range is not whole 64-byte spans");
-    if (r.second / kSpanBytes > (size_t)span_cap - n)
-      throw std::invalid_argument("ttft sketch step: more spans than span_cap");
-    n += r.second / kSpanBytes;
-  }
-  return n;
+  return mislo::plan_ranges(ranges, span_cap, "ttft sketch");
 }
 
 inline void check_step(int n_groups, int group_cap) {
