@@ -361,11 +361,54 @@ class PyLane {
     py::gil_scoped_release nogil;
     t().sync();
   }
+  // ---- checkpoint (steplane.h): the same four calls for every tracker ----
+  // enqueue a snapshot behind the steps issued so far; returns its ticket
+  int64_t snapshot() {
+    T& tr = t();
+    py::gil_scoped_release nogil;
+    return tr.lane().snapshot(tr.host_words());
+  }
+  bool snapshot_ready(int64_t ticket) { return t().lane().snapshot_ready(ticket); }
+  // header and payload as bytes; waits for the transfer
+  py::bytes snapshot_image(int64_t ticket) {
+    T& tr = t();
+    const uint8_t* p;
+    {
+      py::gil_scoped_release nogil;
+      p = tr.lane().snapshot_image(ticket);
+    }
+    return py::bytes(reinterpret_cast<const char*>(p), tr.lane().image_bytes());
+  }
+  float snapshot_kernel_ms() { return t().lane().snapshot_kernel_ms(); }
+  size_t image_bytes() { return t().lane().image_bytes(); }
+  // Take an image, before the first step only; ValueError names what does not fit, with nothing changed.
+  // Returns the index the next step gets.
+  int64_t restore(py::buffer image) {
+    T& tr = t();
+    const py::buffer_info bi = image.request();
+    if (bi.ndim != 1 || bi.strides[0] != bi.itemsize) throw std::invalid_argument("restore: a contiguous one-dimensional buffer");
+    const size_t bytes = (size_t)bi.size * (size_t)bi.itemsize;
+    py::gil_scoped_release nogil;
+    return tr.lane().restore(bi.ptr, bytes, [&tr](const lane::ImageHeader& h) { tr.set_host_words(h.host, (int)h.n_host); }).step;
+  }
+  // blocks of the checkpoint kernels, at most (tests: 1 forces the grid-stride path)
+  void set_checkpoint_blocks(int max_blocks) { t().lane().set_checkpoint_blocks(max_blocks); }
   void close() {
     if (t_) {
       py::gil_scoped_release nogil;
       t_.reset();
     }
+  }
+  // the checkpoint calls of a tracker's class, once for all eleven
+  template <class PyT>
+  static void def_checkpoint(py::class_<PyT>& c) {
+    c.def("snapshot", &PyT::snapshot)
+        .def("snapshot_ready", &PyT::snapshot_ready)
+        .def("snapshot_image", &PyT::snapshot_image)
+        .def("snapshot_kernel_ms", &PyT::snapshot_kernel_ms)
+        .def("image_bytes", &PyT::image_bytes)
+        .def("restore", &PyT::restore)
+        .def("set_checkpoint_blocks", &PyT::set_checkpoint_blocks);
   }
 
  protected:
@@ -1140,10 +1183,35 @@ PYBIND11_MODULE(_mislo_agent, m) {
   m.attr("SIGREC_BYTES") = (int)sizeof(SigRec);
   m.attr("RING_STATE") =
       py::make_tuple("first_busy", "foreign", "def_ctx", "def_trace", "discarded", "events", "other_shard");
+  // the checkpoint image of a side tracker (steplane_host.h namespace lane)
+  m.attr("LANE_IMAGE_HEADER_BYTES") = (int64_t)sizeof(lane::ImageHeader);
+  m.attr("LANE_IMAGE_VERSION") = lane::kVersion;
+  m.def("lane_digest", [](py::buffer payload) {
+    const py::buffer_info bi = payload.request();
+    if (bi.ndim != 1 || bi.strides[0] != bi.itemsize) throw std::invalid_argument("lane_digest: a contiguous one-dimensional buffer");
+    const size_t bytes = (size_t)bi.size * (size_t)bi.itemsize;
+    if (bytes % lane::kChunk) throw std::invalid_argument("lane_digest: whole 16-byte chunks");
+    return lane::digest(bi.ptr, bytes);
+  });
+  // (kind, fingerprint, step, [array bytes], [field values], [host words], payload bytes, digest) of an image's header
+  m.def("lane_image_header", [](py::buffer image) {
+    const py::buffer_info bi = image.request();
+    if (bi.ndim != 1 || bi.strides[0] != bi.itemsize || (size_t)bi.size * (size_t)bi.itemsize < sizeof(lane::ImageHeader))
+      throw std::invalid_argument("lane_image_header: shorter than a header");
+    lane::ImageHeader h;
+    std::memcpy(&h, bi.ptr, sizeof(h));
+    if (h.magic != lane::kMagic || h.n_segments > (uint32_t)lane::kMaxSegments || h.n_fields > (uint32_t)lane::kMaxFields ||
+        h.n_host > (uint32_t)lane::kHostWords)
+      throw std::invalid_argument("lane_image_header: not an image header");
+    return py::make_tuple(std::string(lane::kind_name(h.kind)), h.fingerprint, h.step,
+                          std::vector<uint64_t>(h.seg_bytes, h.seg_bytes + h.n_segments),
+                          std::vector<int64_t>(h.fields, h.fields + h.n_fields), std::vector<int64_t>(h.host, h.host + h.n_host),
+                          h.payload_bytes, h.digest);
+  });
   m.attr("OPENREQ_LDS_GROUPS") = openreq::kLdsGroups;
   m.attr("OPENREQ_MAX_PROBES") = openreq::kMaxProbes;
   m.attr("OPENREQ_STATS") = (int)openreq::kStats;
-  py::class_<PyOpenRequests>(m, "OpenRequests")
+  PyOpenRequests::def_checkpoint(py::class_<PyOpenRequests>(m, "OpenRequests")
       .def(py::init<int, int64_t, int, int, int, double, double, double>(), py::arg("device") = 0,
            py::arg("cap") = (int64_t)1 << 20, py::arg("span_cap") = 16384, py::arg("group_cap") = 64,
            py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("ttl_ms") = 120000.0,
@@ -1155,7 +1223,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyOpenRequests::step_ms)
       .def("entries", &PyOpenRequests::entries)
       .def("sync", &PyOpenRequests::sync)
-      .def("close", &PyOpenRequests::close);
+      .def("close", &PyOpenRequests::close));
   m.attr("SLISKETCH_K") = slisketch::kK;
   m.attr("SLISKETCH_LO_KEY") = slisketch::kLo;
   m.attr("SLISKETCH_STATS") = (int)slisketch::kStats;
@@ -1166,7 +1234,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
     m.attr("SLISKETCH_EDGES") = py::tuple(edges);
     m.attr("SLISKETCH_PERMILLE") = py::tuple(q);
   }
-  py::class_<PySliSketch>(m, "SliSketch")
+  PySliSketch::def_checkpoint(py::class_<PySliSketch>(m, "SliSketch")
       .def(py::init<int, int, int, int, int>(), py::arg("device") = 0, py::arg("span_cap") = 16384,
            py::arg("group_cap") = 64, py::arg("windows") = 150, py::arg("n_buffers") = 3)
       .def("step", &PySliSketch::step, py::arg("spans"), py::arg("n_groups"))
@@ -1176,13 +1244,13 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("rolling", &PySliSketch::rolling)
       .def("window_hist", &PySliSketch::window_hist)
       .def("sync", &PySliSketch::sync)
-      .def("close", &PySliSketch::close);
+      .def("close", &PySliSketch::close));
   m.attr("EXEMPLAR_MAX_K") = exemplars::kMaxK;
   m.attr("EXEMPLAR_MAX_H") = exemplars::kMaxH;
   m.attr("EXEMPLAR_LDS_GROUPS") = exemplars::kLdsGroups;
   m.attr("EXEMPLAR_ROW_BYTES") = exemplars::kRowBytes;
   m.attr("EXEMPLAR_STATS") = (int)exemplars::kStats;
-  py::class_<PyExemplarTracker>(m, "ExemplarTracker")
+  PyExemplarTracker::def_checkpoint(py::class_<PyExemplarTracker>(m, "ExemplarTracker")
       .def(py::init<int, int, int, int64_t, int, int, bool>(), py::arg("device") = 0, py::arg("k") = 3,
            py::arg("windows") = 3, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("n_buffers") = 3,
            py::arg("lds") = true)
@@ -1192,14 +1260,14 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyExemplarTracker::step_ms)
       .def("resident", &PyExemplarTracker::resident)
       .def("sync", &PyExemplarTracker::sync)
-      .def("close", &PyExemplarTracker::close);
+      .def("close", &PyExemplarTracker::close));
   m.attr("PODRANK_MAX_K") = podrank::kMaxK;
   m.attr("PODRANK_MAX_H") = podrank::kMaxH;
   m.attr("PODRANK_ROW_BYTES") = podrank::kRowBytes;
   m.attr("PODRANK_STATS") = (int)podrank::kStats;
   m.attr("PODRANK_LDS_SLOTS") = podrank::kLdsSlots;
   m.def("podrank_slot_of", [](uint32_t g, uint32_t pod, uint32_t slots) { return podrank::slot_of(g, pod, slots); });
-  py::class_<PyPodRankTracker>(m, "PodRankTracker")
+  PyPodRankTracker::def_checkpoint(py::class_<PyPodRankTracker>(m, "PodRankTracker")
       .def(py::init<int, int, int, int64_t, int64_t, int, int, double, bool>(), py::arg("device") = 0, py::arg("k") = 3,
            py::arg("windows") = 3, py::arg("pair_cap") = 4096, py::arg("span_cap") = 16384, py::arg("group_cap") = 64,
            py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("lds") = true)
@@ -1209,12 +1277,12 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyPodRankTracker::step_ms)
       .def("resident", &PyPodRankTracker::resident)
       .def("sync", &PyPodRankTracker::sync)
-      .def("close", &PyPodRankTracker::close);
+      .def("close", &PyPodRankTracker::close));
   m.attr("ONSET_ROW_BYTES") = onset::kRowBytes;
   m.attr("ONSET_STATS") = (int)onset::kStats;
   m.attr("ONSET_LDS_SLOTS") = onset::kLdsSlots;
   m.attr("ONSET_BINS") = py::make_tuple(onset::kMinBins, onset::kMaxBins);
-  py::class_<PyOnsetTracker>(m, "OnsetTracker")
+  PyOnsetTracker::def_checkpoint(py::class_<PyOnsetTracker>(m, "OnsetTracker")
       .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, double, int64_t, bool>(),
            py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_ns") = (int64_t)125000000,
            py::arg("ref_ppm") = (int64_t)20000, py::arg("alarm") = (int64_t)3, py::arg("span_cap") = 16384,
@@ -1226,14 +1294,14 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyOnsetTracker::step_ms)
       .def("resident", &PyOnsetTracker::resident)
       .def("sync", &PyOnsetTracker::sync)
-      .def("close", &PyOnsetTracker::close);
+      .def("close", &PyOnsetTracker::close));
   m.attr("DECODESLI_K") = decodesli::kK;
   m.attr("DECODESLI_STATS") = (int)decodesli::kStats;
   m.attr("DECODESLI_LDS_SLOTS") = decodesli::kLdsSlots;
   m.attr("DECODESLI_PER_LANE") = decodesli::kPerLane;
   m.def("decodesli_bucket_of", [](uint32_t u) { return decodesli::bucket_of(u); });
   m.def("decodesli_tpot_slo_us", [](double ms) { return decodesli::tpot_slo_us(ms); });
-  py::class_<PyDecodeSliTracker>(m, "DecodeSliTracker")
+  PyDecodeSliTracker::def_checkpoint(py::class_<PyDecodeSliTracker>(m, "DecodeSliTracker")
       .def(py::init<int, int64_t, int, int, int, double, double, bool>(), py::arg("device") = 0,
            py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 150, py::arg("n_buffers") = 3,
            py::arg("slo_ms") = 800.0, py::arg("tpot_slo_ms") = 100.0, py::arg("lds") = true)
@@ -1244,7 +1312,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyDecodeSliTracker::step_ms)
       .def("resident", &PyDecodeSliTracker::resident)
       .def("sync", &PyDecodeSliTracker::sync)
-      .def("close", &PyDecodeSliTracker::close);
+      .def("close", &PyDecodeSliTracker::close));
   m.attr("DRIFT_K") = drift::kK;
   m.attr("DRIFT_ROW_STRIDE") = drift::kRowStride;
   m.attr("DRIFT_STATS") = (int)drift::kStats;
@@ -1276,7 +1344,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       py::arg("n_r"), py::arg("n_b"), py::arg("base_fill"), py::arg("slow_num"), py::arg("fast_num"), py::arg("q_recent"),
       py::arg("q_base"), py::arg("crit") = 4.0, py::arg("min_shift") = 2, py::arg("min_recent") = 30,
       py::arg("min_base") = 100, py::arg("min_base_windows") = 10);
-  py::class_<PyDriftTracker>(m, "DriftTracker")
+  PyDriftTracker::def_checkpoint(py::class_<PyDriftTracker>(m, "DriftTracker")
       .def(py::init<int, int64_t, int, int, int, int, int, double, int, int64_t, int64_t, int, int64_t, bool>(),
            py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("recent") = 10,
            py::arg("gap") = 10, py::arg("baseline") = 300, py::arg("n_buffers") = 3, py::arg("crit") = 4.0,
@@ -1289,7 +1357,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyDriftTracker::step_ms)
       .def("resident", &PyDriftTracker::resident)
       .def("sync", &PyDriftTracker::sync)
-      .def("close", &PyDriftTracker::close);
+      .def("close", &PyDriftTracker::close));
   m.attr("ERRSLI_CLASSES") = errsli::kClasses;
   m.attr("ERRSLI_MAX_PAIRS") = errsli::kMaxPairs;
   m.attr("ERRSLI_STATS") = (int)errsli::kStats;
@@ -1314,7 +1382,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
     c.span_cap = (int)span_cap, c.group_cap = group_cap, c.windows = windows;
     return errsli::device_bytes(c);
   });
-  py::class_<PyErrorSliTracker>(m, "ErrorSliTracker")
+  PyErrorSliTracker::def_checkpoint(py::class_<PyErrorSliTracker>(m, "ErrorSliTracker")
       .def(py::init<int, int64_t, int, int, int, double, const std::vector<std::tuple<int64_t, int64_t, int64_t>>&, int64_t,
                     int64_t, bool>(),
            py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 3600,
@@ -1329,7 +1397,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyErrorSliTracker::step_ms)
       .def("resident", &PyErrorSliTracker::resident)
       .def("sync", &PyErrorSliTracker::sync)
-      .def("close", &PyErrorSliTracker::close);
+      .def("close", &PyErrorSliTracker::close));
   m.attr("LOADSLI_ROW_BYTES") = loadsli::kRowBytes;
   m.attr("LOADSLI_STATS") = (int)loadsli::kStats;
   m.attr("LOADSLI_LDS_SLOTS") = loadsli::kLdsSlots;
@@ -1364,7 +1432,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
     return loadsli::device_bytes(bins, (int)span_cap, group_cap);
   });
   m.def("loadsli_ring_records_max", [](int bins, int64_t bin_us) { return loadsli::default_ring_records_max(bins, bin_us); });
-  py::class_<PyLoadSliTracker>(m, "LoadSliTracker")
+  PyLoadSliTracker::def_checkpoint(py::class_<PyLoadSliTracker>(m, "LoadSliTracker")
       .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int, int, int64_t,
                     bool>(),
            py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_us") = 500000, py::arg("settle_bins") = 30,
@@ -1379,7 +1447,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyLoadSliTracker::step_ms)
       .def("resident", &PyLoadSliTracker::resident)
       .def("sync", &PyLoadSliTracker::sync)
-      .def("close", &PyLoadSliTracker::close);
+      .def("close", &PyLoadSliTracker::close));
   m.attr("SATCURVE_ROW_BYTES") = satcurve::kRowBytes;
   m.attr("SATCURVE_STATS") = (int)satcurve::kStats;
   m.attr("SATCURVE_LEVELS") = satcurve::kK;
@@ -1432,7 +1500,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
     for (const auto& s : steps) p.take(s.first, (size_t)s.second);
     return p.after(q_hi, (size_t)n);
   });
-  py::class_<PySaturationTracker>(m, "SaturationTracker")
+  PySaturationTracker::def_checkpoint(py::class_<PySaturationTracker>(m, "SaturationTracker")
       .def(py::init<int, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double, int64_t, int, int, int64_t,
                     int64_t, bool>(),
            py::arg("device") = 0, py::arg("bins") = 1024, py::arg("bin_us") = 500000, py::arg("settle_bins") = 30,
@@ -1447,7 +1515,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PySaturationTracker::step_ms)
       .def("resident", &PySaturationTracker::resident)
       .def("sync", &PySaturationTracker::sync)
-      .def("close", &PySaturationTracker::close);
+      .def("close", &PySaturationTracker::close));
   m.attr("RETRSLI_K") = retrsli::kK;
   m.attr("RETRSLI_STATS") = (int)retrsli::kStats;
   m.attr("RETRSLI_CELLS") = retrsli::kCells;
@@ -1476,7 +1544,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
     return std::vector<size_t>{l.cells, l.cells_roll, l.sum_r, l.sum_t, l.sum_r_roll, l.sum_t_roll, l.sli, l.sli_roll, l.q_r_win,
                                l.q_r_roll, l.q_m_win, l.q_m_roll, l.state, l.age, l.stats, l.words};
   });
-  py::class_<PyRetrievalSliTracker>(m, "RetrievalSliTracker")
+  PyRetrievalSliTracker::def_checkpoint(py::class_<PyRetrievalSliTracker>(m, "RetrievalSliTracker")
       .def(py::init<int, int64_t, int, int, int, double, double, int64_t, int64_t, int64_t, int64_t, bool>(),
            py::arg("device") = 0, py::arg("span_cap") = 16384, py::arg("group_cap") = 64, py::arg("windows") = 150,
            py::arg("n_buffers") = 3, py::arg("slo_ms") = 800.0, py::arg("retrieval_budget_ms") = 200.0,
@@ -1489,7 +1557,7 @@ PYBIND11_MODULE(_mislo_agent, m) {
       .def("step_ms", &PyRetrievalSliTracker::step_ms)
       .def("resident", &PyRetrievalSliTracker::resident)
       .def("sync", &PyRetrievalSliTracker::sync)
-      .def("close", &PyRetrievalSliTracker::close);
+      .def("close", &PyRetrievalSliTracker::close));
   py::class_<PyEngine>(m, "WindowEngine")
       .def(py::init<int, int, int, int, int, int, int, double, double, int, int, bool, bool, int, float, double, int,
                     int, int, int, int, bool>(),

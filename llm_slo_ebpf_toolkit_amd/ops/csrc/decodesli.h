@@ -58,6 +58,10 @@ class DecodeSliTracker {
   // the rolling rows, table and sums and the ring position (synchronous; tests)
   decodesli::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const decodesli::Config& config() const { return cfg_; }
   const decodesli::Layout& result_layout() const { return lay_; }
   uint32_t tpot_slo_us() const { return slo_us_; }

@@ -197,6 +197,7 @@ DecodeSliTracker::DecodeSliTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("decode sli", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(decodesli::fingerprint(cfg));
   slo_us_ = decodesli::tpot_slo_us(cfg.tpot_slo_ms);
   const size_t rows = (size_t)cfg.windows + 2, G = (size_t)cfg.group_cap;
   hist_ = lane_.zeroed<uint32_t>(rows * G * kK);

@@ -115,6 +115,21 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)layout(c.group_cap).words * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kDecodeSli;
+  f.fields = {field("group_cap", c.group_cap),
+              field("windows", c.windows),
+              real_field("slo_ms", c.slo_ms),
+              real_field("tpot_slo_ms", c.tpot_slo_ms),
+              field("buckets", kK)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.windows < 1 || c.windows > 4096) throw std::invalid_argument("decode sli: windows must be in [1, 4096]");
   if (c.group_cap < 1 || c.group_cap > 65536) throw std::invalid_argument("decode sli: group_cap must be in [1, 65536]");

@@ -67,6 +67,10 @@ class DriftTracker {
   // the recent and baseline rows, fill, position, hold and the ring position (synchronous; tests)
   drift::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const drift::Config& config() const { return cfg_; }
   const drift::Layout& result_layout() const { return lay_; }
 

@@ -263,6 +263,7 @@ DriftTracker::DriftTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("ttft drift", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(drift::fingerprint(cfg));
   const size_t G = (size_t)cfg.group_cap;
   hist_ = lane_.zeroed<uint32_t>((size_t)state_rows(cfg) * G * kRowStride);
   words_ = lane_.zeroed<uint32_t>(4 * G);

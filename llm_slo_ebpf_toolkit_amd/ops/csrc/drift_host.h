@@ -163,6 +163,27 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)layout(c.group_cap).words * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kDrift;
+  f.fields = {field("group_cap", c.group_cap),
+              field("recent", c.recent),
+              field("gap", c.gap),
+              field("baseline", c.baseline),
+              real_field("crit", c.crit),
+              field("min_shift", c.min_shift),
+              field("min_recent", c.min_recent),
+              field("min_base", c.min_base),
+              field("min_base_windows", c.min_base_windows),
+              field("hold_max", c.hold_max),
+              field("row_stride", kRowStride)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.recent < 1 || c.recent > 1024) throw std::invalid_argument("ttft drift: recent windows must be in [1, 1024]");
   if (c.gap < 1 || c.gap > 1024) throw std::invalid_argument("ttft drift: gap windows must be in [1, 1024]");

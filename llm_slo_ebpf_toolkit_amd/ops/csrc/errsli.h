@@ -57,6 +57,10 @@ class ErrorSliTracker {
   // the rolling counts, the pairs' sums, the ages and the ring position (synchronous; tests)
   errsli::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const errsli::Config& config() const { return cfg_; }
   const errsli::Layout& result_layout() const { return lay_; }
   uint32_t budget_ppm() const { return budget_; }

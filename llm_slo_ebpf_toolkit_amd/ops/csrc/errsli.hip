@@ -166,6 +166,7 @@ ErrorSliTracker::ErrorSliTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("error sli", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(errsli::fingerprint(cfg));
   budget_ = errsli::budget_ppm(cfg.target);
   const size_t rows = (size_t)cfg.windows + 2, G = (size_t)cfg.group_cap;
   rows_ = lane_.zeroed<uint32_t>(rows * G * kRowWords);

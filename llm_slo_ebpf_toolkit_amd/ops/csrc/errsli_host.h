@@ -116,6 +116,27 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)c.group_cap * (kSumWords + 1) * 4 + (uint64_t)layout(c.group_cap).words * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  static const char* const pair_names[kMaxPairs][3] = {{"pair 0 long", "pair 0 short", "pair 0 factor_milli"},
+                                                       {"pair 1 long", "pair 1 short", "pair 1 factor_milli"},
+                                                       {"pair 2 long", "pair 2 short", "pair 2 factor_milli"},
+                                                       {"pair 3 long", "pair 3 short", "pair 3 factor_milli"}};
+  lane::Fingerprint f;
+  f.kind = lane::kErrSli;
+  f.fields = {field("group_cap", c.group_cap), field("windows", c.windows), lane::real_field("target", c.target),
+              field("min_requests", c.min_requests), field("bad_mask", c.bad_mask), field("pairs", (int64_t)c.pairs.size()),
+              field("classes", kClasses)};
+  for (size_t p = 0; p < c.pairs.size() && p < (size_t)kMaxPairs; ++p) {
+    f.fields.push_back(field(pair_names[p][0], c.pairs[p].long_windows));
+    f.fields.push_back(field(pair_names[p][1], c.pairs[p].short_windows));
+    f.fields.push_back(field(pair_names[p][2], c.pairs[p].factor_milli));
+  }
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.windows < 1 || c.windows > 32768) throw std::invalid_argument("error sli: windows must be in [1, 32768]");
   if (c.group_cap < 1 || c.group_cap > 65536) throw std::invalid_argument("error sli: group_cap must be in [1, 65536]");

@@ -54,6 +54,10 @@ class ExemplarTracker {
   // (synchronous; tests)
   std::pair<std::vector<exemplars::Row>, std::vector<uint32_t>> resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const exemplars::Config& config() const { return cfg_; }
   const exemplars::Layout& result_layout() const { return lay_; }
   int64_t steps() const { return lane_.steps(); }

@@ -195,6 +195,7 @@ ExemplarTracker::ExemplarTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap, cfg.k)),
       lane_("request exemplars", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(exemplars::fingerprint(cfg));
   const size_t G = (size_t)cfg.group_cap, K = (size_t)cfg.k, H = (size_t)cfg.windows;
   keys_ = lane_.zeroed<unsigned long long>(G * K);
   count_ = lane_.zeroed<uint32_t>(G);

@@ -88,6 +88,19 @@ inline uint64_t device_bytes(const Config& c) {
   return ((uint64_t)c.windows + 2) * (uint64_t)c.group_cap * (uint64_t)c.k * kRowBytes;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  lane::Fingerprint f;
+  f.kind = lane::kExemplars;
+  f.fields = {field("group_cap", c.group_cap),
+              field("windows", c.windows),
+              field("k", c.k),
+              field("row_bytes", kRowBytes)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.k < 1 || c.k > kMaxK) throw std::invalid_argument("request exemplars: k must be in [1, 8]");
   if (c.windows < 1 || c.windows > kMaxH) throw std::invalid_argument("request exemplars: windows must be in [1, 16]");

@@ -24,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
 #include <vector>
 
 #include "loadsli_host.h"
@@ -58,6 +59,17 @@ class LoadSliTracker {
   // the ring and what goes with it (synchronous; tests)
   loadsli::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane, and the host integers kept between steps: q_hi, q_first and the
+  // spans the ring's bound counts (restored as if all of them had come with the last step: never fewer)
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const {
+    return {q_hi_, q_first_, q_hi_ == loadsli::kNoBin ? 0 : pop_.after(q_hi_, 0)};
+  }
+  void set_host_words(const int64_t* w, int n) {
+    if (n != 3 || w[2] < 0) throw std::invalid_argument("load sli image: host words");
+    q_hi_ = w[0], q_first_ = w[1];
+    if (q_hi_ != loadsli::kNoBin) pop_.take(q_hi_, (size_t)w[2]);
+  }
   int64_t q_hi() const { return q_hi_; }
   const loadsli::Config& config() const { return cfg_; }
   const loadsli::Layout& result_layout() const { return lay_; }

@@ -254,6 +254,7 @@ LoadSliTracker::LoadSliTracker(const Config& cfg)
       lay_(layout(cfg.group_cap)),
       pop_((uint32_t)cfg.bins, cfg.ring_records_max),
       lane_("load sli", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 2) {
+  lane_.identify(loadsli::fingerprint(cfg), 3);
   const size_t cells = (size_t)cfg.group_cap * (size_t)cfg.bins, G = (size_t)cfg.group_cap;
   counts_ = lane_.zeroed<unsigned long long>(cells);
   idle_ = lane_.zeroed<unsigned long long>(cells);

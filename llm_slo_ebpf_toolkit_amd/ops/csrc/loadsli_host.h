@@ -239,6 +239,25 @@ inline uint64_t device_bytes(int bins, int span_cap, int group_cap) {
 }
 inline uint64_t device_bytes(const Config& c) { return device_bytes(c.bins, c.span_cap, c.group_cap); }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  lane::Fingerprint f;
+  f.kind = lane::kLoadSli;
+  f.fields = {field("group_cap", c.group_cap),
+              field("bins", c.bins),
+              field("bin_us", c.bin_us),
+              field("settle_bins", c.settle_bins),
+              field("recent_bins", c.recent_bins),
+              field("min_base_bins", c.min_base_bins),
+              field("factor_milli", c.factor_milli),
+              field("min_requests", c.min_requests),
+              field("min_conc_milli", c.min_conc_milli),
+              field("ring_records_max", c.ring_records_max)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.bins < kMinBins || c.bins > kMaxBins || (c.bins & (c.bins - 1)) != 0)
     throw std::invalid_argument("load sli: bins must be a power of two in [64, 8192]");

@@ -24,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
 #include <vector>
 
 #include "mislo_common.h"
@@ -56,6 +57,15 @@ class OnsetTracker {
   // the ring and q_hi (synchronous; tests)
   onset::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane, and the host integers kept between steps: q_hi and the spans the
+  // ring's bound counts (restored as if all of them had come with the last step: never fewer than were)
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {q_hi_, q_hi_ == onset::kNoBin ? 0 : pop_.after(q_hi_, 0)}; }
+  void set_host_words(const int64_t* w, int n) {
+    if (n != 2 || w[1] < 0) throw std::invalid_argument("breach onset image: host words");
+    q_hi_ = w[0];
+    if (q_hi_ != onset::kNoBin) pop_.take(q_hi_, (size_t)w[1]);
+  }
   int64_t q_hi() const { return q_hi_; }
   const onset::Config& config() const { return cfg_; }
   const onset::Layout& result_layout() const { return lay_; }

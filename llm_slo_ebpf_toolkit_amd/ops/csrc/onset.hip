@@ -193,6 +193,7 @@ OnsetTracker::OnsetTracker(const Config& cfg)
       lay_(layout(cfg.group_cap)),
       pop_((uint32_t)cfg.bins, cfg.ring_records_max),
       lane_("breach onset", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 2) {
+  lane_.identify(onset::fingerprint(cfg), 2);
   ring_ = lane_.zeroed<unsigned long long>((size_t)cfg.group_cap * (size_t)cfg.bins);
   lane_.ready();
 }

@@ -159,6 +159,23 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)layout(c.group_cap).words * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kOnset;
+  f.fields = {field("group_cap", c.group_cap),
+              field("bins", c.bins),
+              field("bin_ns", c.bin_ns),
+              field("ref_ppm", c.ref_ppm),
+              field("alarm", c.alarm),
+              real_field("slo_ms", c.slo_ms),
+              field("ring_records_max", c.ring_records_max)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.bins < kMinBins || c.bins > kMaxBins || (c.bins & (c.bins - 1)) != 0)
     throw std::invalid_argument("breach onset: bins must be a power of two in [64, 8192]");

@@ -21,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
 #include <vector>
 
 #include "mislo_common.h"
@@ -71,6 +72,13 @@ class OpenRequests {
   void entries(std::vector<uint64_t>& key, std::vector<int64_t>& t, std::vector<uint32_t>& grp,
                std::vector<uint32_t>& state);
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane, and the host integer kept between steps: which table is current
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {cur_}; }
+  void set_host_words(const int64_t* w, int n) {
+    if (n != 1 || (w[0] != 0 && w[0] != 1)) throw std::invalid_argument("open-request image: host words");
+    cur_ = (int)w[0];
+  }
   const openreq::Config& config() const { return cfg_; }
   const openreq::Layout& result_layout() const { return lay_; }
   int64_t steps() const { return lane_.steps(); }

@@ -233,6 +233,7 @@ OpenRequests::OpenRequests(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("open-request", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 0) {
+  lane_.identify(openreq::fingerprint(cfg), 1);
   const size_t cap = (size_t)cfg.cap;
   for (Table& tb : tb_) {
     tb.key = lane_.zeroed<unsigned long long>(cap);

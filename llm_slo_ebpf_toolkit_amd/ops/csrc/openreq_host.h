@@ -54,6 +54,22 @@ struct Config {
 
 inline int64_t ms_to_ns(double ms) { return (int64_t)std::llround(ms * 1e6); }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kOpenReq;
+  f.fields = {field("cap", c.cap),
+              field("group_cap", c.group_cap),
+              real_field("slo_ms", c.slo_ms),
+              real_field("ttl_ms", c.ttl_ms),
+              real_field("reorder_ms", c.reorder_ms),
+              field("max_probes", kMaxProbes)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.cap < kMaxProbes || c.cap > (int64_t(1) << 28) || (c.cap & (c.cap - 1)) != 0)
     throw std::invalid_argument("open-request table: cap must be a power of two in [64, 2^28]");

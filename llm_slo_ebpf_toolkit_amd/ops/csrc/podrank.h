@@ -68,6 +68,10 @@ class PodRankTracker {
   // the horizon's H pair lists, slot = step % windows, in no particular order (synchronous; tests)
   std::vector<podrank::PairList> resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const podrank::Config& config() const { return cfg_; }
   const podrank::Layout& result_layout() const { return lay_; }
 

@@ -344,6 +344,7 @@ PodRankTracker::PodRankTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap, cfg.k)),
       lane_("pod breakdown", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(podrank::fingerprint(cfg));
   wslots_ = window_slots(cfg), rslots_ = recent_slots(cfg);
   const size_t G = (size_t)cfg.group_cap, K = (size_t)cfg.k, H = (size_t)cfg.windows;
   win_ = zeroed_pairs(wslots_);

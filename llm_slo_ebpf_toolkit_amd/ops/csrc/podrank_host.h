@@ -145,6 +145,22 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)layout(c.group_cap, c.k).words * 4 + (H + 1) * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kPodRank;
+  f.fields = {field("group_cap", c.group_cap),
+              field("windows", c.windows),
+              field("k", c.k),
+              field("pair_cap", c.pair_cap),
+              real_field("slo_ms", c.slo_ms),
+              field("entry_bytes", (int64_t)kEntryBytes)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.k < 1 || c.k > kMaxK) throw std::invalid_argument("pod breakdown: k must be in [1, 8]");
   if (c.windows < 1 || c.windows > kMaxH) throw std::invalid_argument("pod breakdown: windows must be in [1, 16]");

@@ -62,6 +62,10 @@ class RetrievalSliTracker {
   // the rolling rows, counters, sums, verdicts and the ring position (synchronous; tests)
   retrsli::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const retrsli::Config& config() const { return cfg_; }
   const retrsli::Layout& result_layout() const { return lay_; }
   uint32_t slo_units() const { return slo_u_; }

@@ -245,6 +245,7 @@ RetrievalSliTracker::RetrievalSliTracker(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("retrieval sli", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 1) {
+  lane_.identify(retrsli::fingerprint(cfg));
   slo_u_ = units_of_ms((float)cfg.slo_ms);
   budget_u_ = retrsli::budget_units(cfg.retrieval_budget_ms);
   const size_t rows = (size_t)cfg.windows + 2, G = (size_t)cfg.group_cap;

@@ -192,6 +192,26 @@ inline uint64_t device_bytes(const Config& c) {
          (uint64_t)c.group_cap * 2 * 4 + block_bytes(c.group_cap);
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap or lds.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  using lane::real_field;
+  lane::Fingerprint f;
+  f.kind = lane::kRetrSli;
+  f.fields = {field("group_cap", c.group_cap),
+              field("windows", c.windows),
+              real_field("slo_ms", c.slo_ms),
+              real_field("retrieval_budget_ms", c.retrieval_budget_ms),
+              field("budget_ppm", c.budget_ppm),
+              field("coverage_ppm", c.coverage_ppm),
+              field("dominance_ppm", c.dominance_ppm),
+              field("min_requests", c.min_requests),
+              field("buckets", kK),
+              field("cell_stride", kCellStride)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.windows < 1 || c.windows > 4096) throw std::invalid_argument("retrieval sli: windows must be in [1, 4096]");
   if (c.group_cap < 1 || c.group_cap > 65536) throw std::invalid_argument("retrieval sli: group_cap must be in [1, 65536]");

@@ -31,6 +31,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <stdexcept>
 #include <vector>
 
 #include "mislo_common.h"
@@ -67,6 +68,20 @@ class SaturationTracker {
   // the ring, the generations and what goes with them (synchronous; tests)
   satcurve::Resident resident();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane, and the host integers kept between steps: q_hi, q_first, the two
+  // generations' epochs and the spans the two bounds count (restored as if all of them had come with the
+  // last step: never fewer than were)
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const {
+    const bool none = q_hi_ == satcurve::kNoBin;
+    return {q_hi_, q_first_, gens_.epoch[0], gens_.epoch[1], none ? 0 : ring_pop_.after(q_hi_, 0),
+            none ? 0 : curve_pop_.after(q_hi_, 0)};
+  }
+  void set_host_words(const int64_t* w, int n) {
+    if (n != 6 || w[4] < 0 || w[5] < 0) throw std::invalid_argument("saturation curve image: host words");
+    q_hi_ = w[0], q_first_ = w[1], gens_.epoch[0] = w[2], gens_.epoch[1] = w[3];
+    if (q_hi_ != satcurve::kNoBin) ring_pop_.take(q_hi_, (size_t)w[4]), curve_pop_.take(q_hi_, (size_t)w[5]);
+  }
   int64_t q_hi() const { return q_hi_; }
   const satcurve::Config& config() const { return cfg_; }
   const satcurve::Layout& result_layout() const { return lay_; }

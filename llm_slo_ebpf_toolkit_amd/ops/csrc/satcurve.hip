@@ -326,6 +326,7 @@ SaturationTracker::SaturationTracker(const Config& cfg)
       ring_pop_((uint32_t)cfg.bins, cfg.ring_records_max),
       curve_pop_(cfg.epoch_bins, cfg.curve_records_max),
       lane_("saturation curve", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 2) {
+  lane_.identify(satcurve::fingerprint(cfg), 6);
   const size_t cells = (size_t)cfg.group_cap * (size_t)cfg.bins, G = (size_t)cfg.group_cap;
   counts_ = lane_.zeroed<u64>(cells);
   idle_ = lane_.zeroed<u64>(cells);

@@ -53,6 +53,10 @@ class SliSketch {
   std::vector<uint32_t> rolling();
   std::vector<uint32_t> window_hist();
   void sync() { lane_.sync(); }
+  // checkpoint (steplane.h): the lane; this tracker keeps no host integers between steps
+  StepLane& lane() { return lane_; }
+  std::vector<int64_t> host_words() const { return {}; }
+  void set_host_words(const int64_t*, int) {}
   const slisketch::Config& config() const { return cfg_; }
   const slisketch::Layout& result_layout() const { return lay_; }
   int64_t steps() const { return lane_.steps(); }

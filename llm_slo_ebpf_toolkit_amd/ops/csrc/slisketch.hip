@@ -151,6 +151,7 @@ SliSketch::SliSketch(const Config& cfg)
     : cfg_(cfg),
       lay_(layout(cfg.group_cap)),
       lane_("ttft sketch", checked(cfg).device, cfg.n_buffers, cfg.span_cap, lay_.words, 0) {
+  lane_.identify(slisketch::fingerprint(cfg));
   row_words_ = (size_t)cfg.group_cap * kRowStride;
   hist_ = lane_.zeroed<uint32_t>(device_bytes(cfg) / 4);
   sum_ = lane_.zeroed<unsigned long long>((size_t)cfg.group_cap);

@@ -109,6 +109,18 @@ inline size_t device_bytes(const Config& c) {
   return ((size_t)c.windows + 2) * (size_t)c.group_cap * (size_t)kRowStride * 4;
 }
 
+// What an image of this tracker's state depends on (steplane_host.h lane::Fingerprint): every field that
+// shapes the state or its meaning, and the layout's constants; not device, n_buffers, span_cap.
+inline lane::Fingerprint fingerprint(const Config& c) {
+  using lane::field;
+  lane::Fingerprint f;
+  f.kind = lane::kSliSketch;
+  f.fields = {field("group_cap", c.group_cap),
+              field("windows", c.windows),
+              field("row_stride", kRowStride)};
+  return f;
+}
+
 inline void validate(const Config& c) {
   if (c.windows < 1 || c.windows > 4096) throw std::invalid_argument("ttft sketch: windows must be in [1, 4096]");
   if (c.span_cap <= 0 || c.span_cap > (1 << 24)) throw std::invalid_argument("ttft sketch: span_cap out of range");

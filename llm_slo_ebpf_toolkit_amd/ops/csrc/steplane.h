@@ -23,11 +23,27 @@
 //   publish  k_lane_publish: the result block into the slot's pinned host block by vector stores, the
 //            block cleared from `clear_from16` on for the next step; then finish(),
 //   finish   hipGetLastError, record `end`, wait for `copied`: the ranges belong to the caller again.
+//
+// Checkpoint (steplane_host.h namespace lane, docs/TRACKER_CHECKPOINT.md). Everything a tracker keeps
+// between steps on the device is an array it took with zeroed(), so the lane can save and restore it
+// without knowing the tracker. zeroed_bytes records (pointer, bytes rounded up to 16); ready() puts one
+// (pointer, image offset, chunks) entry per array but the result block into a segment table in device
+// memory, and the checkpoint kernels index by that table alone -- never by a size or offset read from an
+// image.
+//   snapshot  on the lane's stream, after the last step: k_lane_snapshot gathers the arrays into one
+//             device staging image by 16-byte loads and stores and folds the payload's digest in the same
+//             pass; a copy stream of the lane's waits for that kernel's event and brings staging and digest
+//             to a pinned host image in one hipMemcpyAsync. A step issued right after neither waits for
+//             the transfer nor shows in the image. One snapshot may be pending.
+//   restore   before the first step only: the host checks the header (no HIP call before that), uploads
+//             the payload to staging, k_lane_digest digests it there, the host compares, and only then
+//             k_lane_restore scatters staging into the arrays. A refused restore has changed nothing.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -56,6 +72,11 @@ class StepLane {
   struct Step {
     int64_t index;
     int slot;
+  };
+  // one array of the checkpoint image: where it lies, where its copy lies in the payload, its 16-byte chunks
+  struct Segment {
+    uint4* ptr;
+    unsigned long long off16, n16;
   };
 
   // block_words: uint32 words of the result block, whole 16-byte stores
@@ -86,6 +107,26 @@ class StepLane {
   float ms(int64_t i, Event from, Event to);
   void sync();
 
+  // ---- checkpoint ----
+  // who the image belongs to, and how many host integers the tracker keeps between steps; before ready()
+  void identify(const lane::Fingerprint& fp, int n_host = 0) { fp_ = fp, n_host_ = n_host; }
+  // Enqueue a snapshot behind the steps issued so far; `host_words` are the tracker's own integers as they
+  // stand after those steps. Returns a ticket. Refused while an earlier snapshot is unread.
+  int64_t snapshot(const std::vector<int64_t>& host_words = {});
+  bool snapshot_ready(int64_t ticket);
+  // the image (header and payload), `image_bytes()` long, valid until the next snapshot; waits for it
+  const uint8_t* snapshot_image(int64_t ticket);
+  size_t image_bytes() const { return sizeof(lane::ImageHeader) + payload_bytes_; }
+  // device time of the last snapshot's gather and digest kernel, ms; after snapshot_image()
+  float snapshot_kernel_ms();
+  // Take an image: only before the first step. Throws std::invalid_argument, with nothing changed, when
+  // the image is not this lane's, its digest fails or `accept` (the tracker's check of its host words,
+  // called before anything is scattered) throws; returns the header (step index, host words).
+  lane::ImageHeader restore(const void* image, size_t bytes, const std::function<void(const lane::ImageHeader&)>& accept);
+  // blocks of the checkpoint kernels, at most (tests: 1 forces the grid-stride path)
+  void set_checkpoint_blocks(int max_blocks);
+  const lane::Fingerprint& fingerprint() const { return fp_; }
+
   int64_t steps() const { return slots_.next(); }
   hipStream_t stream() const { return st_; }
   Span* spans() const { return spans_; }
@@ -99,6 +140,7 @@ class StepLane {
     return events_[(size_t)slot * (size_t)per_slot_ + (size_t)e];
   }
   void release();
+  void ensure_staging();
 
   int device_;
   int per_slot_;  // events per slot
@@ -108,6 +150,21 @@ class StepLane {
   Span* spans_ = nullptr;
   uint32_t* block_ = nullptr;
   std::vector<void*> arrays_;  // zeroed(), in allocation order (the result block is the last)
+  std::vector<size_t> array_bytes_;  // of each, rounded up to 16
+  // checkpoint
+  lane::Fingerprint fp_;
+  int n_host_ = 0;
+  lane::ImageHeader mine_;       // what this lane's images carry (ready())
+  Segment* table_ = nullptr;     // device: one entry per array but the result block
+  int n_segments_ = 0;
+  size_t payload_bytes_ = 0;
+  uint8_t* staging_ = nullptr;   // device: payload, then the digest's 16 bytes (first snapshot or restore)
+  uint8_t* image_ = nullptr;     // pinned host: header, payload, digest
+  hipStream_t copy_st_ = nullptr;
+  hipEvent_t snap_begin_ = nullptr, snap_gathered_ = nullptr, snap_done_ = nullptr;
+  int64_t tickets_ = 0;          // snapshots taken
+  bool pending_ = false, stepped_ = false;
+  int ckpt_blocks_ = 1024;
   std::vector<uint32_t*> host_;
   std::vector<hipEvent_t> events_;  // [slot][per_slot_]
 };

@@ -11,8 +11,10 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class DriftTracker:
+
+class DriftTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets; ``results`` per step index."""
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, recent: int = 10, gap: int = 10, baseline: int = 300,

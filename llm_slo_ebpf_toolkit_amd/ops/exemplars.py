@@ -10,8 +10,10 @@ from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class ExemplarTracker:
+
+class ExemplarTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets; ``results`` per step index."""
 
     def __init__(self, k: int = 3, windows: int = 3, span_cap: int = 16384, group_cap: int = 64, n_buffers: int = 3,

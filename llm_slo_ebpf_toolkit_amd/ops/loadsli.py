@@ -11,8 +11,10 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class LoadSliTracker:
+
+class LoadSliTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets and the cut's time; ``results`` per
     step index."""
 

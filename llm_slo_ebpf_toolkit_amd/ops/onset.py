@@ -11,8 +11,10 @@ from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class OnsetTracker:
+
+class OnsetTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets and the cut's time; ``results`` per
     step index."""
 

@@ -10,8 +10,10 @@ from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class PodRankTracker:
+
+class PodRankTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets; ``results`` per step index."""
 
     def __init__(self, k: int = 3, windows: int = 3, pair_cap: int = 4096, span_cap: int = 16384, group_cap: int = 64,

@@ -12,8 +12,10 @@ from typing import Dict, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class RetrievalSliTracker:
+
+class RetrievalSliTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets; ``results`` per step index."""
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, windows: int = 150, n_buffers: int = 3,

@@ -12,8 +12,10 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .lanecheckpoint import LaneCheckpoint
 
-class SaturationTracker:
+
+class SaturationTracker(LaneCheckpoint):
     """``step`` per window with the span ranges the engine gets and the cut's time; ``results`` per
     step index."""
 

@@ -44,6 +44,7 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 from .slisketch import EMPTY, PERMILLE, QUANTILE_NAMES, rank_buckets  # noqa: F401 - the sketch's rank rule
 
 K = 336
@@ -185,8 +186,14 @@ def _gather(ranges) -> np.ndarray:
     return b.view(records.SPAN) if len(b) else np.zeros(0, records.SPAN)
 
 
-class DecodeSliOracle:
+class DecodeSliOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/decodesli_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "decode sli"
+    FINGERPRINT = ("group_cap", "windows", "slo_ms", "tpot_slo_ms")
+    STATE = ("roll", "cells_roll", "sum_roll", "held", "n")
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, windows: int = 150, n_buffers: int = 3,
                  slo_ms: float = 800.0, tpot_slo_ms: float = 100.0, device: int = 0, lds: bool = True):

@@ -47,6 +47,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 from . import slisketch
 from .slisketch import EMPTY, K, PERMILLE, ROW_STRIDE, bucket_of, rank_buckets  # noqa: F401 - the sketch's rules
 
@@ -237,8 +238,14 @@ def statistic(recent: np.ndarray, base: np.ndarray):
     return out[0][0], out[1][0], out[0][1], out[1][1]
 
 
-class DriftOracle:
+class DriftOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/drift_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "ttft drift"
+    FINGERPRINT = ("group_cap", "cfg")
+    STATE = ("near", "recent", "base_ring", "base", "base_fill", "base_pos", "hold", "prev", "n")
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, recent: int = 10, gap: int = 10, baseline: int = 300,
                  n_buffers: int = 3, crit: Optional[float] = None, min_shift: Optional[int] = None,

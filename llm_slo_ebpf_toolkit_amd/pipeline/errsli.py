@@ -43,6 +43,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 
 CLASSES = ("ok", "client", "cancelled", "throttled", "timeout", "unavailable", "server", "other")
 N_CLASSES = 8
@@ -244,8 +245,14 @@ def _gather(ranges) -> np.ndarray:
     return b.view(records.SPAN) if len(b) else np.zeros(0, records.SPAN)
 
 
-class ErrorSliOracle:
+class ErrorSliOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/errsli_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "error sli"
+    FINGERPRINT = ("group_cap", "windows", "target", "pairs", "min_requests", "bad_mask")
+    STATE = ("ring", "roll", "sums", "age", "n")
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, windows: int = 3600, n_buffers: int = 3,
                  target: float = 0.999, pairs: Sequence[Pair] = DEFAULT_PAIRS, min_requests: int = 20,

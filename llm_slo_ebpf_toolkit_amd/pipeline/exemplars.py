@@ -35,6 +35,7 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 
 MAX_K = 8                    # exemplars per service and list
 MAX_H = 16                   # windows of the horizon: H * K <= 128, two candidates per lane of one wave
@@ -120,8 +121,14 @@ def rows_of(spans: np.ndarray, index: np.ndarray) -> np.ndarray:
     return r
 
 
-class ExemplarOracle:
+class ExemplarOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/exemplars_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "request exemplars"
+    FINGERPRINT = ("group_cap", "windows", "k")
+    STATE = ("rows", "held", "n")
 
     def __init__(self, k: int = 3, windows: int = 3, span_cap: int = 16384, group_cap: int = 64, n_buffers: int = 3,
                  device: int = 0):

@@ -70,6 +70,7 @@ from typing import Deque, Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 from .onset import advance, cleared, oldest_bin
 
 MIN_BINS, MAX_BINS = 64, 8192
@@ -265,8 +266,15 @@ def summary(row, bin_us: int, recent_bins: int) -> Dict[str, object]:
                                 "base": svc_ms(row["busy_base"], row["done_base"])}}
 
 
-class LoadSliOracle:
+class LoadSliOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/loadsli_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "load sli"
+    FINGERPRINT = ("group_cap", "bins", "bin_us", ("settle_bins", "settle"), ("recent_bins", "recent"), "min_base_bins",
+                   ("factor_milli", "f"), "min_requests", "min_conc_milli", "ring_records_max")
+    STATE = ("counts", "idle", "carry", "age", "prev_state", "q_hi", "q_first", "held", "n")
 
     def __init__(self, bins: int = 1024, bin_us: int = 500_000, settle_bins: int = 30, recent_bins: int = 30,
                  min_base_bins: int = 60, factor_milli: int = 1500, min_requests: int = 20, min_conc_milli: int = 1000,

@@ -50,6 +50,7 @@ from typing import Deque, Dict, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 
 MIN_BINS, MAX_BINS = 64, 8192
 MIN_BIN_NS, MAX_BIN_NS = 1_000_000, 60_000_000_000
@@ -236,8 +237,14 @@ def scan_rows(cells: np.ndarray, q_hi: int, ref_ppm: int, alarm: int) -> np.ndar
     return np.array([_row(n[g], b[g], q0, h, S[g]) for g in range(C)], ONSET_ROW).reshape(C)
 
 
-class OnsetOracle:
+class OnsetOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/onset_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "breach onset"
+    FINGERPRINT = ("group_cap", "bins", "bin_ns", "ref_ppm", "alarm", "slo_ms", "ring_records_max")
+    STATE = ("cells", "q_hi", "held", "n")
 
     def __init__(self, bins: int = 1024, bin_ns: int = 125_000_000, ref_ppm: int = 20000, alarm: int = 3,
                  span_cap: int = 16384, group_cap: int = 64, n_buffers: int = 3, slo_ms: float = 800.0,

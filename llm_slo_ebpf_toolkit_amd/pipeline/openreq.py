@@ -35,6 +35,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 
 OPEN, COUNTED, RESOLVED = 1, 2, 3
 STATE_NAMES = {OPEN: "open", COUNTED: "counted", RESOLVED: "resolved"}
@@ -95,11 +96,17 @@ def _gather(ranges) -> np.ndarray:
     return b.view(records.SPAN) if len(b) else np.zeros(0, records.SPAN)
 
 
-class OpenRequestOracle:
+class OpenRequestOracle(OracleCheckpoint):
     """The tracker's rules over a dict (see the module docstring). ``cap`` bounds the rows a step
     may hold, removed ones included: the device's table probes at most MAX_PROBES slots, which is
     the whole table at ``cap`` <= MAX_PROBES (there the two agree on ``dropped_full``); a larger
     device table can also drop a start whose probe run is full while the table is not."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/openreq_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "open-request"
+    FINGERPRINT = ("cap", "group_cap", "slo_ms", "ttl_ns", "reorder_ns")
+    STATE = ("tab", "n")
 
     def __init__(self, cap: int = 1 << 20, span_cap: int = 16384, group_cap: int = 64, n_buffers: int = 3,
                  slo_ms: float = 800.0, ttl_ms: float = 120000.0, reorder_ms: float = 2000.0, device: int = 0):

@@ -41,6 +41,7 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 from .oracle import milli_units
 
 MAX_K = 8
@@ -236,8 +237,14 @@ def scope_of(pairs: np.ndarray, group_cap: int, k: int) -> Dict[str, np.ndarray]
             "pods_b": np.bincount(g[hot], minlength=C).astype(np.uint32), "k_top": k_top, "top": top}
 
 
-class PodRankOracle:
+class PodRankOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/podrank_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "pod breakdown"
+    FINGERPRINT = ("group_cap", "windows", "k", "pair_cap", "slo_ms")
+    STATE = ("lists", "hist", "n")
 
     def __init__(self, k: int = 3, windows: int = 3, pair_cap: int = 4096, span_cap: int = 16384, group_cap: int = 64,
                  n_buffers: int = 3, slo_ms: float = 800.0, device: int = 0):

@@ -50,6 +50,7 @@ from ..collector import records
 from .decodesli import K, bucket_of, lower, representative  # noqa: F401 - the histograms' rule
 from .errsli import budget_ppm  # noqa: F401 - the error budget of an SLO target, in millionths
 from .slisketch import EMPTY, PERMILLE, QUANTILE_NAMES, rank_buckets  # noqa: F401 - the sketch's rank rule
+from .trackerstate import OracleCheckpoint
 
 UNITS_PER_MS = 100.0
 UNIT_MAX = (1 << 24) - 1
@@ -257,8 +258,14 @@ def _gather(ranges) -> np.ndarray:
     return b.view(records.SPAN) if len(b) else np.zeros(0, records.SPAN)
 
 
-class RetrievalSliOracle:
+class RetrievalSliOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/retrsli_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "retrieval sli"
+    FINGERPRINT = ("group_cap", "windows", "slo_ms", "retrieval_budget_ms", "th")
+    STATE = ("roll_r", "roll_m", "cells_roll", "sli_roll", "sum_roll", "verdict", "age", "held", "n")
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, windows: int = 150, n_buffers: int = 3,
                  slo_ms: float = 800.0, retrieval_budget_ms: float = 200.0, budget_ppm: int = 10000,
@@ -277,7 +284,7 @@ class RetrievalSliOracle:
         self.cells_roll = np.zeros((group_cap, N_CELLS), np.int64)
         self.sli_roll = np.zeros(group_cap, np.int64)
         self.sum_roll = np.zeros((group_cap, 2), np.uint64)
-        self.state = np.zeros(group_cap, np.uint32)
+        self.verdict = np.zeros(group_cap, np.uint32)  # the published state of the step before
         self.age = np.zeros(group_cap, np.uint32)
         self.held: Dict[int, tuple] = {}  # step % windows -> that step's rows
         self.res: Dict[int, Tuple[int, dict]] = {}
@@ -342,8 +349,8 @@ class RetrievalSliOracle:
         self.sli_roll += sli
         self.held[slot] = (hist_r, hist_m, cells, sums, sli)
         state = np.array([state_of(self.cells_roll[j], self.sli_roll[j], **self.th) for j in range(C)], np.uint32)
-        self.age = np.array([age_of(int(state[j]), int(self.state[j]), int(self.age[j])) for j in range(C)], np.uint32)
-        self.state = state
+        self.age = np.array([age_of(int(state[j]), int(self.verdict[j]), int(self.age[j])) for j in range(C)], np.uint32)
+        self.verdict = state
         res = {"cells": cells.astype(np.uint32), "cells_roll": self.cells_roll.astype(np.uint32),
                "sum_r": sums[:, 0].copy(), "sum_t": sums[:, 1].copy(), "sum_r_roll": self.sum_roll[:, 0].copy(),
                "sum_t_roll": self.sum_roll[:, 1].copy(), "sli": sli.astype(np.uint32), "sli_roll": self.sli_roll.astype(np.uint32),
@@ -386,7 +393,7 @@ class RetrievalSliOracle:
         row the next step replaces."""
         return {"rows_r": self.roll_r.astype(np.uint32), "rows_m": self.roll_m.astype(np.uint32),
                 "cells": self.cells_roll.astype(np.uint32), "sli": self.sli_roll.astype(np.uint32),
-                "sums": self.sum_roll.copy(), "state": self.state.copy(), "age": self.age.copy(),
+                "sums": self.sum_roll.copy(), "state": self.verdict.copy(), "age": self.age.copy(),
                 "pos": self.n % self.windows}
 
     def sync(self) -> None:

@@ -65,6 +65,7 @@ from .loadsli import (MAX_BIN_US, MAX_BINS, MAX_LATENCY_MS, MIN_BIN_US, MIN_BINS
                       default_ring_records_max, dur_us, ordered, per_bin)
 from .loadsli import ranges_of as load_ranges_of
 from .onset import advance, cleared, oldest_bin
+from .trackerstate import OracleCheckpoint
 
 K = 160
 MAX_U = 8191
@@ -245,8 +246,15 @@ def summary(row, curve: np.ndarray) -> Dict[str, object]:
                       for l in np.nonzero(np.asarray(curve)[:, 0])[0].tolist()]}
 
 
-class SaturationOracle:
+class SaturationOracle(OracleCheckpoint):
     """The tracker's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/satcurve_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "saturation curve"
+    FINGERPRINT = ("group_cap", "bins", "bin_us", ("settle_bins", "settle"), ("recent_bins", "recent"), "epoch_bins",
+                   "budget_ppm", "min_requests", ("slo_ms", "slo"), "ring_records_max", "curve_records_max")
+    STATE = ("counts", "idle", "sli", "carry", "gen", "gen_epoch", "age", "q_hi", "q_first", "held", "epochs", "n")
 
     def __init__(self, bins: int = 1024, bin_us: int = 500_000, settle_bins: int = 30, recent_bins: int = 30,
                  epoch_bins: int = 43200, budget_ppm: int = 10000, min_requests: int = 200, slo_ms: float = 800.0,

@@ -37,6 +37,7 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 
 from ..collector import records
+from .trackerstate import OracleCheckpoint
 from .oracle import milli_units
 
 KEY_SHIFT = 19
@@ -132,8 +133,14 @@ def _gather(ranges) -> np.ndarray:
     return b.view(records.SPAN) if len(b) else np.zeros(0, records.SPAN)
 
 
-class SliSketchOracle:
+class SliSketchOracle(OracleCheckpoint):
     """The sketch's rules in numpy (see the module docstring), with the device handle's interface."""
+
+    # checkpoint (pipeline/trackerstate.py): the fields ops/csrc/slisketch_host.h fingerprint() covers, and what is
+    # kept between steps
+    KIND = "ttft sketch"
+    FINGERPRINT = ("group_cap", "windows")
+    STATE = ("roll", "held", "last", "n")
 
     def __init__(self, span_cap: int = 16384, group_cap: int = 64, windows: int = 150, n_buffers: int = 3,
                  device: int = 0):

@@ -450,6 +450,7 @@ class WindowPipeline:
                 from .retrsli import RetrievalSliOracle
 
                 self.retr = RetrievalSliOracle(**rkw)
+        self.window_len_ms = float(window_ms)
         # the side trackers are fixed from here on: copy_ahead asks once per window and half
         self._no_side_tracker = all(t is None for t in (self.tracker, self.sketch, self.exemplars, self.pods, self.onset,
                                                         self.decode, self.drift, self.errors, self.load, self.sat,
@@ -934,11 +935,86 @@ class WindowPipeline:
         return summarize(self.eng.totals())
 
     # ---- checkpoint / resume (utils/checkpoint.py) ------------------------------------------
+    # name (the modules' under ops/ and pipeline/), attribute, the buffer-to-step map, and for a horizon
+    # counted in windows how many it holds (None: a ring of absolute time, the next cut advances it)
+    SIDE_TRACKERS = (("openreq", "tracker", "_open", None), ("slisketch", "sketch", "_sli", lambda t: t.windows),
+                     ("exemplars", "exemplars", "_ex", lambda t: t.windows), ("podrank", "pods", "_pod", lambda t: t.windows),
+                     ("onset", "onset", "_onset", None), ("decodesli", "decode", "_dec", lambda t: t.windows),
+                     ("drift", "drift", "_drf", lambda t: t.R + t.L + t.B), ("errsli", "errors", "_err", lambda t: t.windows),
+                     ("loadsli", "load", "_load", None), ("satcurve", "sat", "_sat", None),
+                     ("retrsli", "retr", "_retr", lambda t: t.windows))
+
+    def side_trackers(self) -> Dict[str, object]:
+        """The side trackers that are on, by name."""
+        return {name: getattr(self, attr) for name, attr, _m, _w in self.SIDE_TRACKERS if getattr(self, attr) is not None}
+
+    def tracker_states(self, now_ns: Optional[int] = None) -> Tuple[Dict[str, np.ndarray], Dict[str, object]]:
+        """The side trackers' part of ``state()``: one array ``tracker/<name>`` for every tracker that is on,
+        and under ``trackers`` its kind, fingerprint, step index and image bytes; ``saved_unix_ns`` and
+        ``window_ms`` place the horizons in wall time. Nothing at all with no tracker on. The device
+        trackers' snapshots are all enqueued before the first image is waited for."""
+        on = self.side_trackers()
+        if not on:
+            return {}, {}
+        tickets = {name: t.snapshot() for name, t in on.items() if hasattr(t, "snapshot")}
+        arrays, metas = {}, {}
+        for name, t in on.items():
+            if name in tickets:
+                image = t.snapshot_image(tickets[name])
+                arrays[f"tracker/{name}"], metas[name] = image, t.image_meta(image)
+            else:
+                a, metas[name] = t.state()
+                arrays[f"tracker/{name}"] = a["image"]
+        import time
+
+        return arrays, {"trackers": metas, "saved_unix_ns": int(time.time_ns() if now_ns is None else now_ns),
+                        "window_ms": self.window_len_ms}
+
+    def restore_trackers(self, arrays: Dict[str, np.ndarray], meta: Dict[str, object],
+                         now_ns: Optional[int] = None) -> Dict[str, object]:
+        """Resume every side tracker that is on from ``tracker_states()``: ``{"resumed": [names], "fresh":
+        {name: reason}}``. A tracker whose image is missing, another tracker's or another configuration's
+        starts fresh (it has not been touched). A horizon counted in windows then takes ``missed =
+        floor((now - saved_unix_ns) / window_ms)`` empty steps, so that it keeps its meaning in wall time;
+        with ``missed`` at or above the horizon nothing would survive and the tracker starts fresh. The rings
+        of absolute time need nothing: the next cut advances them."""
+        import time
+
+        out: Dict[str, object] = {"resumed": [], "fresh": {}}
+        metas = meta.get("trackers") or {}
+        now = int(time.time_ns() if now_ns is None else now_ns)
+        window_ns = float(meta.get("window_ms", self.window_len_ms)) * 1e6
+        missed = max(0, int((now - int(meta.get("saved_unix_ns", now))) // window_ns)) if window_ns > 0 else 0
+        for name, attr, held, horizon in self.SIDE_TRACKERS:
+            t = getattr(self, attr)
+            if t is None:
+                continue
+            key = f"tracker/{name}"
+            if name not in metas or key not in arrays:
+                out["fresh"][name] = "no saved image"
+            elif float(meta.get("window_ms", self.window_len_ms)) != self.window_len_ms:
+                out["fresh"][name] = f"saved with window_ms {meta.get('window_ms')}, this pipeline {self.window_len_ms}"
+            elif horizon is not None and missed >= horizon(t):
+                out["fresh"][name] = f"{missed} windows missed, the horizon holds {horizon(t)}"
+            else:
+                try:
+                    t.restore_state({"image": arrays[key]}, metas[name])
+                except (ValueError, RuntimeError) as e:
+                    out["fresh"][name] = str(e)
+                    continue
+                if horizon is not None:
+                    for _ in range(missed):  # every row: the rows past the services in use hold nothing
+                        t.step([], t.group_cap)
+                out["resumed"].append(name)
+            getattr(self, held).clear()
+        return out
+
     def state(self) -> Tuple[Dict[str, np.ndarray], Dict[str, object]]:
         """Everything the learned model depends on (arrays, metadata); drains the engine. The
         device refit runs nb windows behind: the statistics of the windows it has not folded
         yet (their all-reduced packets) are added, so the checkpoint holds every finished
-        window (the restored engine refits from them)."""
+        window (the restored engine refits from them). With side trackers on, their horizons too
+        (``tracker_states``)."""
         self.drain()
         c = self.cum_stats
         stats = np.asarray(self.eng.stats_acc(), dtype=np.float64).copy()
@@ -953,11 +1029,17 @@ class WindowPipeline:
         meta = {"model": self.model_name, "seed": self.seed, "learn": self.learn, "windows": self.k,
                 "windows_folded_device": int(self.eng.windows_folded) + len(pending),
                 "windows_folded_host": self.windows_folded_host, "n_domains": N_DOMAINS}
+        t_arrays, t_meta = self.tracker_states()
+        arrays.update(t_arrays)
+        meta.update(t_meta)
         return arrays, meta
 
-    def restore(self, arrays: Dict[str, np.ndarray], meta: Dict[str, object]) -> None:
+    def restore(self, arrays: Dict[str, np.ndarray], meta: Dict[str, object],
+                now_ns: Optional[int] = None) -> Dict[str, object]:
         """Resume from ``state()``: the same model family is required; statistics, the model on
-        the device and the fold counters continue where the checkpoint left them."""
+        the device and the fold counters continue where the checkpoint left them. The side trackers
+        resume as ``restore_trackers`` says, whose report this returns (``now_ns``: the wall clock, a
+        parameter for tests)."""
         if meta.get("model") != self.model_name or int(meta.get("n_domains", N_DOMAINS)) != N_DOMAINS:
             raise ValueError(f"checkpoint of model {meta.get('model')!r} cannot resume {self.model_name!r}")
         # the learned Bayes is refit on the device from the statistics; other models keep the image
@@ -974,6 +1056,7 @@ class WindowPipeline:
                 self.model = LDA.fit(self.cum_stats)
             else:
                 self.model = NaiveBayes.learned(self.cum_stats, **self.learned_kw)
+        return self.restore_trackers(arrays, meta, now_ns)
 
     def save_checkpoint(self, path: str, extra_meta: Optional[Dict[str, object]] = None) -> None:
         from ..utils import checkpoint
@@ -986,7 +1069,7 @@ class WindowPipeline:
         from ..utils import checkpoint
 
         arrays, meta = checkpoint.load(path)
-        self.restore(arrays, meta)
+        meta["tracker_report"] = self.restore(arrays, meta)
         return meta
 
     def host_model(self):
