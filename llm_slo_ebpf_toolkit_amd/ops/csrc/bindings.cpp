@@ -455,6 +455,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("join", &Engine::join, py::arg("spans"), py::arg("n_groups"), py::arg("base_attrs") = py::none())
       .def("posterior", &Engine::posterior)
       .def("accumulate_stats", &Engine::accumulate_stats, py::arg("weights") = py::none())
+      .def("posterior_and_stats", &Engine::posterior_and_stats)
       .def("pack", &Engine::pack)
       .def("run_window", &Engine::run_window, py::arg("events"), py::arg("spans"), py::arg("n_groups"),
            py::arg("with_labels") = true, py::arg("learn") = false, py::arg("wire") = 64)
